@@ -13,10 +13,18 @@ eliminated-signal map exchanged over RCCL; strong scaling); the independent-shar
 its own circuit, no collective; weak scaling) is the extra object `weak_shards`.
 
 Rank 0 prints ONE JSON line with: the roofline of the dominant kernel (HIP events on the library's
-streams, in-kernel algorithmic bytes; head and tail of the ordered elimination split), the
-whole-path roofline B_alg / T_simplify, the HBM-resident rate as an extra key, the CPU baseline (the
-canonical CPU oracle oracle/refcpu.cpp on this box's cores, plus a 1-thread leg on a bounded sample)
-and `bit_exact`: the last timed step's output compared array for array with the oracle's."""
+streams, in-kernel algorithmic bytes; head and tail of the ordered elimination split) and the
+whole-path roofline B_alg / T_simplify -- all read off the timed steps themselves.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes runs of
+its own: the PCIe link probe, the .r1cs writer, the DAG flattening, the templated / 1 M linear / --O1
+circuits, the HBM-resident rate, the weak-scaling shards (N > 1), the CPU baseline (the canonical CPU
+oracle oracle/refcpu.cpp on this box's cores, plus a 1-thread leg on a bounded sample) and
+`bit_exact`: the last timed step's output compared array for array with the oracle's.  Each of them
+keeps its own --no-* switch under --full.
+
+`--dump-outputs DIR` writes the last timed step's result (what rs_engine_simplify handed back) as
+DIR/<name>.npy, see dump_outputs()."""
 from __future__ import annotations
 
 import argparse
@@ -337,6 +345,52 @@ def timed_steps(eng, inp_c, fl, steps, barrier):
     return time.perf_counter() - t0, acc, tot, out, eng.stats()
 
 
+DUMP_ENTRIES = 1 << 17  # --dump-outputs: an array with more entries is written as a sample of this many
+
+
+def _exact_f64(x):
+    """An unsigned integer array (entries along axis 0) as float64 without loss: a 64-bit value becomes
+    its (low, high) 32-bit words, so a field element's 4 limbs become 8 columns."""
+    import numpy as np
+    x = np.ascontiguousarray(x)
+    if x.dtype.itemsize < 8:
+        return x.astype(np.float64)
+    words = 2 * int(np.prod(x.shape[1:], dtype=np.int64))
+    return x.view("<u4").reshape(x.shape[0], words).astype(np.float64)
+
+
+def dump_outputs(dirname: str, arrays, seed: int = 0):
+    """The result of one step (rsio.output_arrays: what rs_engine_simplify returned, compacted to CSR) as
+    DIR/<name>.npy, all float64 and exact (_exact_f64):
+      scalars   n_constraints, n_wires, no_private_inputs_witness, n_labels
+      l2w       the label -> wire map
+      {a,b,c}_ptr / _col / _val   the three CSR blocks (val: one row of 8 words per coefficient)
+      summary   one row per array above, in that order: its number of entries and the (low, high) words
+                of the sum mod 2^64 of all its 32-bit words -- the whole array, not the sample
+    An array with more than DUMP_ENTRIES entries is written as a sample of that many (indices drawn
+    without replacement, sorted, from a generator seeded by `seed` and the array's position, so they
+    depend on the array's length alone): under 40 MB in all at any circuit size."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    items = [("l2w", arrays["l2w"])]
+    for nm in ("a", "b", "c"):
+        ptr, col, val = arrays[nm]
+        items += [(nm + "_ptr", ptr), (nm + "_col", col), (nm + "_val", val.reshape(-1, 4))]
+    np.save(os.path.join(dirname, "scalars.npy"),
+            np.array([arrays[k] for k in ("n_constraints", "n_wires", "npiw", "n_labels")], np.float64))
+    summary = []
+    for i, (name, x) in enumerate(items):
+        x = np.ascontiguousarray(x)
+        n = x.shape[0]
+        s = int(np.sum(x.view("<u4"), dtype=np.uint64)) if x.size else 0
+        summary.append([float(n), float(s & 0xFFFFFFFF), float(s >> 32)])
+        if n > DUMP_ENTRIES:
+            idx = np.sort(np.random.default_rng([seed, i]).choice(n, DUMP_ENTRIES, replace=False))
+            x = x[idx]
+        np.save(os.path.join(dirname, name + ".npy"), _exact_f64(x))
+    np.save(os.path.join(dirname, "summary.npy"), np.array(summary, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -356,7 +410,15 @@ def main():
     ap.add_argument("--no-link", action="store_true", help="skip the PCIe link probe")
     ap.add_argument("--no-hbm", action="store_true", help="skip the HBM-resident extra (profiling passes: host -> host steps only)")
     ap.add_argument("--no-write", action="store_true", help="skip the .r1cs writer extra")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras (link probe, writer, flatten, templated, linear1M, --O1, HBM-resident, "
+                         "weak shards, CPU baseline and bit_exact); without it the --no-* switches have nothing to skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_weak = args.no_flatten = args.no_templated = args.no_o1 = True
+        args.no_linear1m = args.no_link = args.no_hbm = args.no_write = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -411,9 +473,11 @@ def main():
     dt, acc, tot, out, last = timed_steps(eng, pin.c, fl, args.steps, barrier)
     dt, _ = reduce_over_ranks(dist, dt, n_rows, red_dev)
     got = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and (not args.no_cpu or args.dump_outputs):
         import rsio
         got = rsio.output_arrays(out)  # copy of the last timed step's result (the view is reused)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got)
     # the last result written as .r1cs by the device writer (8(d): write timed apart)
     write = None
     if rank == 0 and not args.no_write:

@@ -1,5 +1,5 @@
 set -o pipefail
-# The round-end checks on one GPU box: the GPU test suite, smoke(), the default bench line.
+# The round-end checks on one GPU box: the GPU test suite, smoke(), the bench line with every extra.
 # A step that times out, aborts or faults ends the script (no further GPU step after it).
 O=gpurun_out/${OUT:-final}
 mkdir -p $O
@@ -9,4 +9,4 @@ echo "tests rc=$rc" >> $O/gpu_tests.log
 case $rc in 124|134|137|139) exit $rc ;; esac
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
 echo smoke ok >> $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1

@@ -87,7 +87,7 @@ def main():
     ap.add_argument("--commit", default=None, help="git commit the profiled tree was at")
     ap.add_argument("--calib", default=None, help="profiles/roundN_pmc_calib.json (tools/pmc_calib.py): bytes moved "
                     "from the counters with the factors of the gather / emit patterns instead of FETCH_SIZE x2")
-    ap.add_argument("--bench", default="bench.py --steps K --warmup 0 --no-cpu", help="what the passes ran (for the record)")
+    ap.add_argument("--bench", default="bench.py --full --steps K --warmup 0 --no-cpu", help="what the passes ran (for the record)")
     ap.add_argument("--stats", default=None, help="rocprofv3 --stats kernel_stats.csv of the bench: the groups' coverage")
     args = ap.parse_args()
     fe = per_dispatch(args.fetch_dir, "FETCH_SIZE")
