@@ -1,8 +1,10 @@
 """GPU parity on the fallback paths the synthetic workloads rarely reach:
   * a process_4 cluster longer than the LDS arena replay (cluster.hpp kClLds = 32768 rows), whose
     rows are not consumed by the uniques phase (lane replay in global memory);
-  * dense rows whose work lists outgrow k_big_main's LDS buffers (kBigCap = 512: lane-serial spill)
-    and whose substitutions outgrow the wave composition (kComposeCap: serial composition);
+  * dense rows whose work lists outgrow the ordered loops' LDS buffers (the tail launches
+    k_big_main<256>, the speculative head falls back to d_big_main_cluster<512>: lane-serial spill
+    past either) and whose substitutions outgrow the wave composition (kComposeCap: serial
+    composition); tests/test_gpu_dispatch.py sits exactly on these limits;
   * process_3 clusters between the lane kernel and process_4 (32..349 rows) with long rows;
   * leftovers (rows with only forbidden signals) inside workgroup clusters."""
 import random
