@@ -613,6 +613,10 @@ struct Output {
   std::vector<int32_t> label_to_wire;
   uint64_t n_wires = 0, no_private_inputs_witness = 0;
   uint64_t rounds = 0, n_clusters = 0;
+  // --simplification_substitution (constraint_simplification.rs:9-17): every substitution handed to
+  // log_substitutions (:249, :271, :320 of every round), in that order
+  bool want_log = false;
+  std::vector<Sub> log;
 };
 
 static void simplification(Ctx &X, Input &in, uint32_t flag_s, uint64_t no_rounds, bool old_heur,
@@ -664,6 +668,7 @@ static void simplification(Ctx &X, Input &in, uint32_t flag_s, uint64_t no_round
     for (auto &v : aux)
       for (auto &c : v) lconst.push_back(std::move(c));
   }
+  if (out.want_log) out.log.insert(out.log.end(), eq_subs.begin(), eq_subs.end());
   std::vector<int32_t> eq_idx(S, -1);
   for (size_t i = 0; i < eq_subs.size(); ++i) eq_idx[eq_subs[i].from] = (int32_t)i;
   for (const Sub &sb : eq_subs) X.alg.subs += sb.to.size();
@@ -705,6 +710,7 @@ static void simplification(Ctx &X, Input &in, uint32_t flag_s, uint64_t no_round
     X.alg.subs += rest.size();
     c_subs.push_back(Sub{s, std::move(rest)});
   }
+  if (out.want_log) out.log.insert(out.log.end(), c_subs.begin(), c_subs.end());
   std::vector<int32_t> c_idx(S, -1);
   for (size_t i = 0; i < c_subs.size(); ++i) c_idx[c_subs[i].from] = (int32_t)i;  // last wins
   for (size_t i = 0; i < in.linear.size(); ++i) {
@@ -724,6 +730,7 @@ static void simplification(Ctx &X, Input &in, uint32_t flag_s, uint64_t no_round
     std::vector<Con> cons;
     linear_simplification(X, in.linear, old_heur, subs, cons, &out.n_clusters);
     out.rounds++;
+    if (out.want_log) out.log.insert(out.log.end(), subs.begin(), subs.end());
     for (Sub &s : subs) {
       deleted[s.from] = 1;
       if (relevant[s.from]) l_subs.push_back(std::move(s));
@@ -765,6 +772,7 @@ static void simplification(Ctx &X, Input &in, uint32_t flag_s, uint64_t no_round
     std::vector<Con> constants;
     linear_simplification(X, linear, old_heur, subs, constants, &out.n_clusters);
     out.rounds++;
+    if (out.want_log) out.log.insert(out.log.end(), subs.begin(), subs.end());
     for (const Sub &s : subs) deleted[s.from] = 1;
     for (auto &c : constants) lconst.push_back(std::move(c));
     // for constraint in lconst { for sub in subs { apply } fix }  (:629-634)
@@ -902,6 +910,10 @@ extern "C" {
 
 const char *refcpu_last_error(void) { return g_err.c_str(); }
 
+// 1: refcpu_simplify fills rs_output.log_* when rs_flags.emit_substitution_log is set.  tests/rsio.py
+// looks for this symbol to tell a library built from an older refcpu.cpp, which returns no log.
+int refcpu_log_abi(void) { return 1; }
+
 // The last refcpu_simplify's algorithmic bytes (this thread): out[0] = B_alg, out[1..10] = Z_in, Z_out,
 // subs, app, rowupd, merges (entries), R_in, R_out, max_signal, w (bytes per entry).
 void refcpu_last_alg(uint64_t out[11]) { memcpy(out, g_alg, sizeof g_alg); }
@@ -938,6 +950,7 @@ int refcpu_simplify(const rs_input *in, const rs_flags *fl, int n_threads, rs_ou
               load_block(X, in->nl_c, I.nonlin, 2, false);
     if (!ok) { g_err = "invalid input block"; return RS_E_INVALID; }
     Output O;
+    O.want_log = fl->emit_substitution_log != 0;
     for (const rs_lc *b : {&in->cons_eq, &in->eq, &in->linear, &in->nl_a, &in->nl_b, &in->nl_c}) X.alg.z_in += b->nnz;
     X.alg.r_in = in->cons_eq.n_rows + in->eq.n_rows + in->linear.n_rows + in->nl_a.n_rows;
     auto t0 = std::chrono::steady_clock::now();
@@ -964,6 +977,16 @@ int refcpu_simplify(const rs_input *in, const rs_flags *fl, int n_threads, rs_ou
     memcpy(o->label_to_wire, O.label_to_wire.data(), sizeof(int32_t) * X.max_signal);
     o->n_wires = O.n_wires;
     o->no_private_inputs_witness = O.no_private_inputs_witness;
+    if (O.want_log && !O.log.empty()) {
+      std::vector<Con> tos(O.log.size());
+      o->n_log = O.log.size();
+      o->log_from = (uint32_t *)malloc(sizeof(uint32_t) * O.log.size());
+      for (size_t i = 0; i < O.log.size(); ++i) {
+        o->log_from[i] = O.log[i].from;
+        tos[i].c = std::move(O.log[i].to);
+      }
+      store_block(X.F, tos, 2, o->log_to);
+    }
     *out = o;
     return RS_OK;
   } catch (const std::exception &e) {
@@ -974,8 +997,9 @@ int refcpu_simplify(const rs_input *in, const rs_flags *fl, int n_threads, rs_ou
 
 void refcpu_output_free(rs_output *o) {
   if (!o) return;
-  for (rs_lc *b : {&o->a, &o->b, &o->c}) { free(b->ptr); free(b->col); free(b->val); }
+  for (rs_lc *b : {&o->a, &o->b, &o->c, &o->log_to}) { free(b->ptr); free(b->col); free(b->val); }
   free(o->label_to_wire);
+  free(o->log_from);
   free(o);
 }
 

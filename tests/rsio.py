@@ -188,10 +188,20 @@ def oracle_lib():
     global _ORACLE
     if _ORACLE is None:
         path = os.path.join(ROOT, "oracle", "_ref", "librefcpu.so")
+        import subprocess
         if not os.path.exists(path):
-            import subprocess
             subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
+        else:
+            # a library left from a checkout whose refcpu.cpp had no substitution log (it would hand
+            # back an empty log, not an error) is rebuilt before it is loaded
+            with open(path, "rb") as f:
+                stale = b"refcpu_log_abi" not in f.read()
+            if stale:
+                subprocess.check_call(["make", "-s", "-B", "-C", os.path.join(ROOT, "oracle")])
         lib = C.CDLL(path)
+        lib.refcpu_log_abi.restype = C.c_int
+        if lib.refcpu_log_abi() < 1:
+            raise RuntimeError(f"{path} is older than oracle/refcpu.cpp")
         lib.refcpu_simplify.argtypes = [C.POINTER(RsInput), C.POINTER(RsFlags), C.c_int,
                                         C.POINTER(C.POINTER(RsOutput)), C.POINTER(C.c_double),
                                         C.POINTER(C.c_uint64)]
@@ -221,6 +231,23 @@ def oracle_run(inp: RsInput, fl: RsFlags, threads=1):
         lib.refcpu_output_free(out)
 
 
+def oracle_run_log(inp: RsInput, fl: RsFlags, threads=1):
+    """refcpu with the substitution log on -> (constraints, signal_map,
+    no_private_inputs_witness, [(from, {signal: value})]): the form tests/soundness.py checks."""
+    lib = oracle_lib()
+    out = C.POINTER(RsOutput)()
+    fl2 = RsFlags.from_buffer_copy(fl)
+    fl2.emit_substitution_log = 1
+    rc = lib.refcpu_simplify(C.byref(inp), C.byref(fl2), threads, C.byref(out), None, None)
+    if rc != 0:
+        raise RuntimeError(f"refcpu rc={rc}: {lib.refcpu_last_error().decode()}")
+    try:
+        cons, sm, _, npiw = output_to_py(out.contents)
+        return cons, sm, npiw, output_log(out.contents)
+    finally:
+        lib.refcpu_output_free(out)
+
+
 # --------------------------------------------------------------------------- random systems
 def gen_system(seed: int, p: int, n_sig: int = 60, n_rows: int = 80, n_out: int = 2,
                n_pub: int = 2, big_cluster: int = 0, density: float = 1.0, extra_forb: float = 0.0) -> "R.System":
@@ -228,7 +255,10 @@ def gen_system(seed: int, p: int, n_sig: int = 60, n_rows: int = 80, n_out: int 
     and > 1 with forbidden ends, duplicate/forbidden constant equalities, linear clusters for
     process_3 and (big_cluster >= 350) process_4, non-linear rows that turn linear in round 1 and
     in later rounds, constant-A reductions and coefficient cancellations (small p).  extra_forb: the
-    share of the other signals that are forbidden too (custom-gate signals, forbidden intermediates)."""
+    share of the other signals that are forbidden too (custom-gate signals, forbidden intermediates).
+    The duplicate constant equalities usually contradict each other (x = 3 and x = 5), so about a
+    third of these systems are unsatisfiable and their result keeps one of the two definitions
+    (tests/test_soundness.py counts them); tests/soundness.py's gen_circuit makes satisfiable ones."""
     rng = random.Random(seed)
     S = n_sig + 1
     n_priv = max(1, min(4, n_sig - n_out - n_pub))
