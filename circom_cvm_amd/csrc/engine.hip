@@ -39,6 +39,7 @@
 #include "cluster.hpp"
 #include "writer.hpp"
 #include "maplists.hpp"
+#include "knobs.hpp"
 
 namespace rs {
 
@@ -212,13 +213,40 @@ struct KGroup {
 
 }  // namespace rs
 #include "comm.hpp"
-namespace rs {
-
-
-
-}  // namespace rs
 
 using namespace rs;
+
+// rs_engine::ev: the events that order and time a round's elimination and the frames passes
+enum Ev {
+  kEvFill0, kEvFill1,          // a frames pass / a round's fill on the main stream: start, end
+  kEvElim0, kEvElim1,          // a round's elimination on the main stream: start (the head forks here), end
+  kEvSmallFork,                // the small clusters' stream forks from the main stream
+  kEvTailPrep, kEvTailLoop,    // the tail's first group: after prep + p3_fast, after the ordered loop
+  kEvTailEnd,                  // the tail's chain is done (main stream)
+  kEvHead0, kEvHeadPrep, kEvHeadLoop, kEvHeadEnd,  // the head chain (second stream): start, after the
+                               // preparation, after the ordered loop, after the emit
+  kEvHeadReady,                // the head's preparation is done: the main stream and the giants start
+  kEvLane,                     // after the lane kernel (the small clusters), before the tail
+  kEvReplayFork, kEvReplayJoin,  // the largest clusters' replays on the second stream: fork / join
+  kEvNl0, kEvNl1,              // the overlapped first frames pass: start, end
+  kEvCount
+};
+// rs_engine::pin: the pinned host buffers' slots.  kPinPtr / kPinCol / kPinVal (+ part) and kPinL2w are
+// also the slot numbers fetch_result's `buf` callback is asked for.
+enum PinSlot {
+  kPinPtr = 0,           // a/b/c: row pointers (streamed result: the jump tables)
+  kPinCol = 3,           // a/b/c: columns (streamed result: [early | late])
+  kPinVal = 6,           // a/b/c: values
+  kPinL2w = 9,           // label_to_wire
+  kPinWrite = 11,        // rs_engine_write_r1cs's staging pool
+  kPinLens = 13,         // a/b/c: row lengths (streamed result)
+  kPinReplayMeta = 16,   // the host replay's staging: metadata, rows
+  kPinReplayStage = 17,
+  kPinRead = 18,         // small read-backs (kPinRb bytes, never reallocated)
+  kPinCluster = 19,      // the clustering's read-back
+  kPinFlat = 20,         // rs_engine_flatten_dag's result (19 arrays)
+  kPinCount = 40
+};
 
 struct rs_engine {
   uint64_t pool_want = 0;  // substitution pool size (entries) that fitted last time
@@ -227,8 +255,7 @@ struct rs_engine {
   hipStream_t st = nullptr;
   hipStream_t srd = nullptr;  // host reads (rd): non-blocking, from the pooled queues
   hipStream_t st2 = nullptr;  // the largest clusters' elimination chain runs here, beside the rest
-  hipEvent_t evx[11] = {};    // [0] join-in, [1..4] head chain, [5] after the lane kernel, [6..7] the
-                              // largest replays' fork / join, [8..9] the overlapped frames pass
+  hipEvent_t ev[kEvCount] = {};  // (enum Ev)
   Arena A;
   bool loaded = false;
   bool have_result = false;
@@ -250,7 +277,6 @@ struct rs_engine {
   uint64_t out_nnz[3] = {0, 0, 0};
   uint64_t n_wires = 0, npiw = 0;
   rs_stats stats{};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr, ev4 = nullptr, ev5 = nullptr, ev6 = nullptr, ev7 = nullptr;
   // sharded elimination: this engine is rank `comm->rank` of `comm->world`
   std::unique_ptr<rs::Comm> comm;
   // substitution log of the last run (rs_flags.emit_substitution_log), canonical values
@@ -272,18 +298,15 @@ struct rs_engine {
   bool staged = false;
   const rs_input *hin = nullptr;
   unsigned long long *h_lvl = nullptr;  // pinned: frontier counts of the head's [0..3] / the tail's [4..7] composition levels
-  hipEvent_t ev_lvl[4] = {}, ev_lvlt[4] = {};  // frontier-count events of the head's / the tail's level loops
+  hipEvent_t ev_lvl[4] = {};  // frontier-count events of the head's level loop
   double h2d_wait_ms = 0;
   // pinned result buffers of rs_engine_simplify (grow only) and the view handed out
   struct Pin {
     void *p = nullptr;
     size_t cap = 0;
   };
-  Pin pin[40];  // a/b/c: ptr, col, val; label_to_wire; spare; rs_engine_write_r1cs's two staging buffers;
-                // a/b/c row ends (streamed result); [16..17] the host replay's staging; [18..19] the
-                // clustering's read-backs; [20..38]
-                // rs_engine_flatten_dag's result (19 arrays)
-  rs_input flat_view{};  // rs_engine_flatten_dag's result (views pin[20..38])
+  Pin pin[kPinCount];    // (enum PinSlot)
+  rs_input flat_view{};  // rs_engine_flatten_dag's result (views pin[kPinFlat + 0..18])
   rs_output view{};
   // streamed result (output.hpp; rs_engine_simplify): the storage rows final after round 1 go to
   // pin[3..8] on the copy stream during the later rounds (ev_snap: their D2H is done)
@@ -330,7 +353,7 @@ struct rs_engine {
   hipStream_t str = nullptr;  // the host replay's copies (small; never behind the bulk copies)
   hipStream_t ste = nullptr;  // the small clusters' elimination (k_eliminate), beside the tail's chain
   hipStream_t stg = nullptr;  // the giant clusters' component loops (giant_loop.hpp), beside the head's
-  hipEvent_t evg[2] = {};     // giant path: fork after the head's preparation / join before its inversion
+  hipEvent_t ev_gjoin = nullptr;  // giant path: its loops are done (joined before the head's inversion)
   // per-kernel timing (rs_stats ABI 8): the tail groups' [prep, after prep + p3_fast, after the loop,
   // after the inversion, after the finish]; build_clusters' device span; the giant path's span
   hipEvent_t evt[2][5] = {};
@@ -626,7 +649,6 @@ static void h2d(rs_engine *E, void *dst, const void *src, size_t bytes) {
 }
 
 // ---------------------------------------------------------------- scans
-static void *pin_get(rs_engine *E, int slot, size_t bytes);
 constexpr size_t kPinRb = 128;  // pinned slot 18: small read-backs (one size everywhere: never reallocated)
 static uint64_t excl_scan_u64(rs_engine *E, const uint64_t *in, uint64_t *out, uint64_t n, const char *tag,
                               double *waited = nullptr) {
@@ -635,7 +657,7 @@ static uint64_t excl_scan_u64(rs_engine *E, const uint64_t *in, uint64_t *out, u
   HC(rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E->st));
   void *tmp = E->A.get<uint8_t>(std::string("scan.tmp.") + tag, tb);
   HC(rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E->st));
-  uint64_t *h = (uint64_t *)pin_get(E, 18, kPinRb) + 4;  // pinned read-back words [4..5] (no staged copy)
+  uint64_t *h = (uint64_t *)pin_get(E, kPinRead, kPinRb) + 4;  // pinned read-back words [4..5] (no staged copy)
   HC(hipMemcpyAsync(h, in + n - 1, 8, hipMemcpyDeviceToHost, E->st));
   HC(hipMemcpyAsync(h + 1, out + n - 1, 8, hipMemcpyDeviceToHost, E->st));
   const double t0 = waited ? now_ms() : 0.0;
@@ -657,7 +679,7 @@ struct U3Plus {
 static U3 excl_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, const char *tag, const uint64_t *x_in = nullptr,
                        const uint64_t *x_out = nullptr, uint64_t *x_sum = nullptr) {
   if (n == 0 && !x_sum) return U3{0, 0, 0};
-  uint64_t *h = (uint64_t *)pin_get(E, 18, kPinRb) + 8;
+  uint64_t *h = (uint64_t *)pin_get(E, kPinRead, kPinRb) + 8;
   if (n) {
     size_t tb = 0;
     const U3 zero{0, 0, 0};
@@ -1122,7 +1144,7 @@ struct DevClusters {
   uint32_t *perm = nullptr, *big = nullptr, *small = nullptr, *cid = nullptr;
   uint64_t *cl_off = nullptr;
   uint64_t n_slots = 0, n_big = 0, n_small = 0, tot_nnz = 0;
-  // the largest clusters' row orders are still being replayed on the second stream (evx[7] marks
+  // the largest clusters' row orders are still being replayed on the second stream (ev[kEvReplayJoin] marks
   // the end); only the head -- ordered after the replay on that stream -- reads them until the join
   bool join_pending = false;
   // host copy of the sorted size keys of the kHeadLimit largest clusters (k_cl_sizekey: size in the
@@ -1259,7 +1281,7 @@ static DevClusters gpu_clusters(rs_engine *E, const DRows &V, int old_heur, cons
   HC(hipMemsetAsync(stat, 0, 64, st));
   launch_capped(st, k_cl_count, n, 1024, V, npairs, stat);
   uint64_t *poff = A.get<uint64_t>("cl.poff", n);
-  unsigned long long *hs = (unsigned long long *)pin_get(E, 18, kPinRb);  // pinned: no staged copy
+  unsigned long long *hs = (unsigned long long *)pin_get(E, kPinRead, kPinRb);  // pinned: no staged copy
   HC(hipMemcpyAsync(hs, stat, 16, hipMemcpyDeviceToHost, st));
   const uint64_t P = excl_scan_u64(E, npairs, poff, n, "cl1", &hw);  // (its read-back synchronises)
   mark("pairs");
@@ -1318,7 +1340,7 @@ static DevClusters gpu_clusters(rs_engine *E, const DRows &V, int old_heur, cons
   // the size keys of the largest clusters (the head's; the giant path reads their row counts) and the
   // class counts, into pinned memory in one read-back
   const uint64_t n_top = std::min<uint64_t>(n_cl, kHeadLimit);
-  unsigned long long *hcb = (unsigned long long *)pin_get(E, 19, 8 * (8 + kHeadLimit));
+  unsigned long long *hcb = (unsigned long long *)pin_get(E, kPinCluster, 8 * (8 + kHeadLimit));
   unsigned long long *hc = hcb;
   HC(hipMemcpyAsync(hc, cnt, 40, hipMemcpyDeviceToHost, st));
   if (n_top) HC(hipMemcpyAsync(hcb + 8, sk2, 8 * n_top, hipMemcpyDeviceToHost, st));
@@ -1353,12 +1375,12 @@ static DevClusters gpu_clusters(rs_engine *E, const DRows &V, int old_heur, cons
     uint64_t *d_meta = A.get<uint64_t>("cl.rmeta", kMetaW * nh);
     launch(E->str, k_replay_meta, nh, (const uint64_t *)D.cl_off, (const uint32_t *)(sorted + hc[3]), nh,
            (const uint64_t *)q_off, (const uint32_t *)n_ordered, d_meta);
-    uint64_t *meta = (uint64_t *)pin_get(E, 16, 8 * kMetaW * nh);
+    uint64_t *meta = (uint64_t *)pin_get(E, kPinReplayMeta, 8 * kMetaW * nh);
     HC(hipMemcpyAsync(meta, d_meta, 8 * kMetaW * nh, hipMemcpyDeviceToHost, E->str));
     sync(E->str);
     mark("replay meta");
-    HC(hipEventRecord(E->evx[6], st));
-    HC(hipStreamWaitEvent(E->st2, E->evx[6], 0));
+    HC(hipEventRecord(E->ev[kEvReplayFork], st));
+    HC(hipStreamWaitEvent(E->st2, E->ev[kEvReplayFork], 0));
     std::vector<uint64_t> todo;
     uint64_t tot_q = 0, tot_n = 0;
     for (uint64_t i = 0; i < nh; ++i) {
@@ -1375,7 +1397,7 @@ static DevClusters gpu_clusters(rs_engine *E, const DRows &V, int old_heur, cons
     const uint64_t nt = todo.size();
     if (nt) {
       // staging: qo (tot_n + nt u64), pairs (tot_q u32), rows (tot_n u32), orders (tot_n u32)
-      uint8_t *stg = (uint8_t *)pin_get(E, 17, 8 * (tot_n + nt) + 4 * (tot_q + 2 * tot_n));
+      uint8_t *stg = (uint8_t *)pin_get(E, kPinReplayStage, 8 * (tot_n + nt) + 4 * (tot_q + 2 * tot_n));
       uint64_t *qo = (uint64_t *)stg;
       uint32_t *hst = (uint32_t *)(qo + tot_n + nt), *hsrow = hst + tot_q, *hperm = hsrow + tot_n;
       std::vector<uint64_t> o_q(nt), o_n(nt), o_o(nt);
@@ -1433,10 +1455,10 @@ static DevClusters gpu_clusters(rs_engine *E, const DRows &V, int old_heur, cons
   }
   if (hc[4]) {  // join: the elimination reads every cluster's order -- deferred when every cluster
                 // replayed there is a head cluster (single rank: the head is this rank's largest)
-    HC(hipEventRecord(E->evx[7], E->st2));
+    HC(hipEventRecord(E->ev[kEvReplayJoin], E->st2));
     const bool sharded = E->comm && E->comm->world > 1;
     if (!sharded && hc[3] + hc[4] <= kHeadLimit) D.join_pending = true;
-    else HC(hipStreamWaitEvent(st, E->evx[7], 0));
+    else HC(hipStreamWaitEvent(st, E->ev[kEvReplayJoin], 0));
   }
   // elimination split: clusters of kWaveMin rows or more and the heavy small ones (a prefix of the
   // sort order, k_cl_sizekey) go to the workgroup kernels (process_3 or process_4 per cluster), the
@@ -1711,7 +1733,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
       const uint64_t r = (0xffffffffull - (D.top_keys[i] >> 32)) & 0x7fffffffull;
       if (r >= kGiantRows && !D.order_free.count((uint32_t)(D.top_keys[i] & 0xffffffffull))) giant_rows_sum += r;
     }
-    if (!getenv("RS_GI_NOPOOL")) want = std::max<uint64_t>(want, 192 * giant_rows_sum);
+    if (!env_flag("RS_GI_NOPOOL")) want = std::max<uint64_t>(want, 192 * giant_rows_sum);
   }
   for (int attempt = 0; attempt < 8; ++attempt) {
     P = get_pool(E, want);
@@ -1763,7 +1785,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
     a.row_off = E->A.get<uint64_t>("el.row_off", n_slots);
     a.row_len = E->A.get<uint32_t>("el.row_len", n_slots);
 
-    a.prof = (getenv("RS_DEBUG") || getenv("RS_PROF")) && n_big ? E->A.get<unsigned long long>("el.prof", kProfWords * n_big) : nullptr;
+    a.prof = (env_flag("RS_DEBUG") || env_flag("RS_PROF")) && n_big ? E->A.get<unsigned long long>("el.prof", kProfWords * n_big) : nullptr;
     if (a.prof) HC(hipMemsetAsync(a.prof, 0, 8 * kProfWords * n_big, E->st));
     a.fclk = nullptr;
 #ifdef RS_FINCLK
@@ -1827,11 +1849,11 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
     LevelLoop hl;
     int n_tgroups = 0;  // tail groups launched (their evt events are recorded)
     if (eo.n_clusters) {
-      HC(hipEventRecord(E->ev2, E->st));
+      HC(hipEventRecord(E->ev[kEvElim0], E->st));
       if (n_head) {
-        HC(hipStreamWaitEvent(E->st2, E->ev2, 0));
+        HC(hipStreamWaitEvent(E->st2, E->ev[kEvElim0], 0));
         const unsigned g = (unsigned)n_head;
-        HC(hipEventRecord(E->evx[1], E->st2));
+        HC(hipEventRecord(E->ev[kEvHead0], E->st2));
         {  // the largest process_4 clusters: occurrences / uniques over a 2-D grid first
           const dim3 g2(kWideX, g);
           const uint32_t *ids = d_big;
@@ -1845,10 +1867,10 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         }
         hipLaunchKernelGGL(k_big_prep, dim3(g), dim3(256), 0, E->st2, a, (const uint32_t *)d_big, n_head);
         HC(hipGetLastError());
-        HC(hipEventRecord(E->evx[2], E->st2));
-        HC(hipEventRecord(E->evx[10], E->st2));
+        HC(hipEventRecord(E->ev[kEvHeadPrep], E->st2));
+        HC(hipEventRecord(E->ev[kEvHeadReady], E->st2));
         if (!giants.empty()) {  // beside the speculative loop, joined before the head's inversion
-          HC(hipStreamWaitEvent(E->stg, E->evx[10], 0));
+          HC(hipStreamWaitEvent(E->stg, E->ev[kEvHeadReady], 0));
           HC(hipMemsetAsync(GA.scal + 5, 0, 4, E->stg));  // the merge count over this run's giants
           HC(hipEventRecord(E->evgt[0], E->stg));
           ElimArgs ag = a;
@@ -1859,7 +1881,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
             giant_launch(E, ag, G, D.top_keys[i] & 0xffffffffull, i);
           }
           HC(hipEventRecord(E->evgt[1], E->stg));
-          HC(hipEventRecord(E->evg[1], E->stg));
+          HC(hipEventRecord(E->ev_gjoin, E->stg));
         }
         // the ordered loop: twelve waves reduce rows speculatively against the LDS signal table and
         // commit in pop order (spec_loop.hpp).  12 vs 8 waves (three per SIMD at <= 168 VGPRs, 152 B of
@@ -1867,8 +1889,8 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         // still reducing: 4.5 -> 3.0 ms), templated 26.7 -> 28.1 ms (its chains conflict at distance 1)
         hipLaunchKernelGGL(k_big_spec<12>, dim3(g), dim3(768), 0, E->st2, aspec, (const uint32_t *)d_big, n_head);
         HC(hipGetLastError());
-        HC(hipEventRecord(E->evx[3], E->st2));
-        if (!giants.empty()) HC(hipStreamWaitEvent(E->st2, E->evg[1], 0));
+        HC(hipEventRecord(E->ev[kEvHeadLoop], E->st2));
+        if (!giants.empty()) HC(hipStreamWaitEvent(E->st2, E->ev_gjoin, 0));
         HC(hipEventRecord(E->evgt[2], E->st2));  // the head's composition chain starts (after the giants)
         // one inversion per head cluster
         hipLaunchKernelGGL(k_batch_inv_tree, dim3(g), dim3(256), 0, E->st2, a, (const uint32_t *)d_big, n_head);
@@ -1882,12 +1904,12 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
       // the main stream starts once the head's preparation is done: its short workgroups come after
       // the head's large-LDS ones have found CUs.  The small clusters first (k_eliminate, one lane
       // each), then the tail: the frames pass that follows waits for both.
-      if (n_head) HC(hipStreamWaitEvent(E->st, E->evx[10], 0));
+      if (n_head) HC(hipStreamWaitEvent(E->st, E->ev[kEvHeadReady], 0));
       // the small clusters (one lane each) on their own stream: nothing of the tail's chain reads them
       // (disjoint signals; the pool allocation is atomic), so the chain -- the first frames pass's and
       // hence the result stream's critical path -- starts at once; the main stream joins after it
-      HC(hipEventRecord(E->ev4, E->st));
-      HC(hipStreamWaitEvent(E->ste, E->ev4, 0));
+      HC(hipEventRecord(E->ev[kEvSmallFork], E->st));
+      HC(hipStreamWaitEvent(E->ste, E->ev[kEvSmallFork], 0));
       HC(hipEventRecord(E->ev_sm[0], E->ste));
       if (n_small) {
         uint64_t blocks = (n_small + 63) / 64;
@@ -1896,14 +1918,14 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         HC(hipGetLastError());
       }
       HC(hipEventRecord(E->ev_sm[1], E->ste));
-      HC(hipEventRecord(E->evx[5], E->st));
+      HC(hipEventRecord(E->ev[kEvLane], E->st));
       n_tgroups = 0;
       if (n_tail) {
         // The tail in two groups on two streams: its kTailSplit largest clusters on the main stream
         // (their ordered loops are the tail's latency), the rest -- most of the composition work,
         // which fills the GPU -- beside them on the small clusters' stream, after k_eliminate.  One
         // launch per kernel over all of them made every finish wait for the largest loops.
-        static const uint64_t split = getenv("RS_TAIL_SPLIT") ? strtoull(getenv("RS_TAIL_SPLIT"), nullptr, 10) : kTailSplit;
+        static const uint64_t split = env_u64("RS_TAIL_SPLIT", kTailSplit, 1, UINT64_MAX / 2);  // (0 left the first group empty)
         const uint64_t n_t1 = n_tail > split + split / 4 ? split : n_tail, n_t2 = n_tail - n_t1;
         n_tgroups = n_t2 ? 2 : 1;
         auto tail_group = [&](hipStream_t s, ElimArgs g, const uint32_t *ids, uint64_t n, const char *cls_name, int grp) {
@@ -1920,11 +1942,11 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
           HC(hipMemsetAsync(g.skip, 0, n, s));
           hipLaunchKernelGGL(k_p3_fast, dim3(gb), dim3(256), 0, s, g, ids, n);
           HC(hipGetLastError());
-          if (timed) HC(hipEventRecord(E->ev5, s));
+          if (timed) HC(hipEventRecord(E->ev[kEvTailPrep], s));
           HC(hipEventRecord(ev[1], s));
           hipLaunchKernelGGL(k_big_main<256>, dim3(gm), dim3(64), 0, s, g, ids, n);
           HC(hipGetLastError());
-          if (timed) HC(hipEventRecord(E->ev6, s));
+          if (timed) HC(hipEventRecord(E->ev[kEvTailLoop], s));
           HC(hipEventRecord(ev[2], s));
           {  // the group's clusters flagged in cls, then one inversion per 64 slots across clusters
             uint8_t *cls = E->A.get<uint8_t>(cls_name, eo.n_clusters);
@@ -1965,10 +1987,10 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         hl.ev = E->ev_lvl;
         if (overlap) hl.run(std::min(kHeadGpuLevels, kHeadLevels), false);
       }
-      HC(hipEventRecord(E->ev7, E->st));
+      HC(hipEventRecord(E->ev[kEvTailEnd], E->st));
       HC(hipStreamWaitEvent(E->st, E->ev_sm[2], 0));  // the small clusters' and the tail's second group's, from here on
       if (D.join_pending) {  // the main stream reads the head clusters' orders from here on
-        HC(hipStreamWaitEvent(E->st, E->evx[7], 0));
+        HC(hipStreamWaitEvent(E->st, E->ev[kEvReplayJoin], 0));
         D.join_pending = false;
       }
       // the head's composition: the first (wide) Kahn levels over the whole GPU, the rest in one
@@ -1983,7 +2005,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         }
         hipLaunchKernelGGL(k_big_emit<8>, dim3((unsigned)n_head), dim3(512), 0, E->st2, ah, (const uint32_t *)d_big, n_head);
         HC(hipGetLastError());
-        HC(hipEventRecord(E->evx[4], E->st2));
+        HC(hipEventRecord(E->ev[kEvHeadEnd], E->st2));
         if (g_prof_env) fprintf(stderr, "[rs-prof] head composition: %u level launches\n", hl.levels);
       };
       if (n_head) finish_head();
@@ -2004,8 +2026,8 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         }
         (*overlap)(d_big, n_head, ao);
       }
-      if (n_head) HC(hipStreamWaitEvent(E->st, E->evx[4], 0));
-      HC(hipEventRecord(E->ev3, E->st));
+      if (n_head) HC(hipStreamWaitEvent(E->st, E->ev[kEvHeadEnd], 0));
+      HC(hipEventRecord(E->ev[kEvElim1], E->st));
     }
     // the verdict and the substitution / leftover totals in one read-back
     unsigned long long *d_sums = E->A.get<unsigned long long>("el.sums", 2);
@@ -2028,7 +2050,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
     if ((err & 8) && !(err & kGiErrBounds)) {  // pool exhausted (a bounds violation fails below instead)
       size_t fr_ = 0, tot_ = 0;
       (void)hipMemGetInfo(&fr_, &tot_);
-      if (getenv("RS_PROF")) {
+      if (g_prof_env) {
         unsigned long long used = 0;
         HC(hipMemcpy(&used, P.top, 8, hipMemcpyDeviceToHost));
         fprintf(stderr, "[rs-debug] pool exhausted: cap %llu entries, top %llu, attempt %d\n",
@@ -2067,7 +2089,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
     if (eo.n_clusters) {
       float ms = 0;
       unsigned long long by = 0;
-      HC(hipEventElapsedTime(&ms, E->ev2, E->ev3));
+      HC(hipEventElapsedTime(&ms, E->ev[kEvElim0], E->ev[kEvElim1]));
       float msm = 0;
       HC(hipEventElapsedTime(&msm, E->ev_sm[0], E->ev_sm[1]));
       E->stats.elim_big_ms += ms;  // wall of the workgroup kernels (both streams; the small ones run beside)
@@ -2108,9 +2130,9 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
       }
       if (n_tail) {
         float m0 = 0, m1 = 0, m2 = 0;
-        HC(hipEventElapsedTime(&m0, E->evx[5], E->ev5));
-        HC(hipEventElapsedTime(&m1, E->ev5, E->ev6));
-        HC(hipEventElapsedTime(&m2, E->ev6, E->ev7));
+        HC(hipEventElapsedTime(&m0, E->ev[kEvLane], E->ev[kEvTailPrep]));
+        HC(hipEventElapsedTime(&m1, E->ev[kEvTailPrep], E->ev[kEvTailLoop]));
+        HC(hipEventElapsedTime(&m2, E->ev[kEvTailLoop], E->ev[kEvTailEnd]));
         E->stats.big_prep_ms += m0;
         E->stats.big_main_ms += m1;
         E->stats.big_finish_ms += m2;
@@ -2131,26 +2153,26 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
       if (g_prof_env) {
         float t0 = 0, t1 = 0, t2 = 0, t3 = 0;
         if (n_tail) {
-          HC(hipEventElapsedTime(&t0, E->evx[5], E->ev5));
-          HC(hipEventElapsedTime(&t1, E->ev5, E->ev6));
-          HC(hipEventElapsedTime(&t2, E->ev6, E->ev7));
+          HC(hipEventElapsedTime(&t0, E->ev[kEvLane], E->ev[kEvTailPrep]));
+          HC(hipEventElapsedTime(&t1, E->ev[kEvTailPrep], E->ev[kEvTailLoop]));
+          HC(hipEventElapsedTime(&t2, E->ev[kEvTailLoop], E->ev[kEvTailEnd]));
         }
         HC(hipEventElapsedTime(&t3, E->ev_sm[0], E->ev_sm[1]));
         fprintf(stderr, "[rs-prof] tail(%llu): prep %.2f main %.2f inv+finish %.2f small %.2f", (unsigned long long)n_tail, t0, t1, t2, t3);
         if (n_head) {
           float h0 = 0, h1 = 0, h2 = 0;
-          HC(hipEventElapsedTime(&h0, E->evx[1], E->evx[2]));
-          HC(hipEventElapsedTime(&h1, E->evx[2], E->evx[3]));
-          HC(hipEventElapsedTime(&h2, E->evx[3], E->evx[4]));
+          HC(hipEventElapsedTime(&h0, E->ev[kEvHead0], E->ev[kEvHeadPrep]));
+          HC(hipEventElapsedTime(&h1, E->ev[kEvHeadPrep], E->ev[kEvHeadLoop]));
+          HC(hipEventElapsedTime(&h2, E->ev[kEvHeadLoop], E->ev[kEvHeadEnd]));
           fprintf(stderr, " | head(%llu): prep %.2f main %.2f inv+finish %.2f", (unsigned long long)n_head, h0, h1, h2);
         }
         fprintf(stderr, " | wall %.2f\n", ms);
       }
       if (n_head) {
         float m0 = 0, m1 = 0, m2 = 0;
-        HC(hipEventElapsedTime(&m0, E->evx[1], E->evx[2]));
-        HC(hipEventElapsedTime(&m1, E->evx[2], E->evx[3]));
-        HC(hipEventElapsedTime(&m2, E->evx[3], E->evx[4]));
+        HC(hipEventElapsedTime(&m0, E->ev[kEvHead0], E->ev[kEvHeadPrep]));
+        HC(hipEventElapsedTime(&m1, E->ev[kEvHeadPrep], E->ev[kEvHeadLoop]));
+        HC(hipEventElapsedTime(&m2, E->ev[kEvHeadLoop], E->ev[kEvHeadEnd]));
         E->stats.big_prep_ms += m0;
         E->stats.big_main_ms += m1;
         E->stats.big_finish_ms += m2;
@@ -2158,7 +2180,7 @@ static void run_linear_simplification(rs_engine *E, const DRows &view, int old_h
         E->stats.head_main_ms += m1;
         E->stats.head_launches++;
         float mf = 0;
-        HC(hipEventElapsedTime(&mf, E->evgt[2], E->evx[4]));
+        HC(hipEventElapsedTime(&mf, E->evgt[2], E->ev[kEvHeadEnd]));
         E->stats.head_fin_ms += mf;
         E->stats.head_fin_launches++;
       }
@@ -2477,8 +2499,8 @@ static void snap_start(rs_engine *E) {
     // 128 MiB chunks, two in flight (host -> host medians 44.1-44.3 ms against 44.5-45.6 with 32 MiB
     // chunks, tools/r6_snap_ab.sh): small copies on the other streams are not held behind them
     // (tools/micro/copyq.hip), and fewer chunks leave fewer gaps between them on the link
-    static const size_t chunk = (getenv("RS_SNAP_CHUNK_MB") ? strtoull(getenv("RS_SNAP_CHUNK_MB"), nullptr, 10) : 128ull) << 20;
-    static const int depth = std::max(1, std::min(8, getenv("RS_SNAP_DEPTH") ? atoi(getenv("RS_SNAP_DEPTH")) : 2));
+    static const size_t chunk = (size_t)env_u64("RS_SNAP_CHUNK_MB", 128, 1, 1ull << 20) << 20;
+    static const int depth = (int)env_u64("RS_SNAP_DEPTH", 2, 1, 8);
     if (hipSetDevice(E->device) != hipSuccess) { E->snap_rc = RS_E_HIP; return; }
     int k = 0;
     double prof_ms = 0.0, prof_b = 0.0;
@@ -2573,1538 +2595,7 @@ static void ensure_csr(rs_engine *E) {
   E->csr_ready = true;
 }
 
-static void engine_run(rs_engine *E, const rs_flags *fl) {
-  const uint64_t S = E->S;
-  hipStream_t st = E->st;
-  E->stats = rs_stats{};
-  E->stats.world = E->comm ? (uint64_t)E->comm->world : 1;
-  for (int g = 1; g < 3; ++g) {  // (kg[0]: the load's checks, recorded before the run)
-    E->kg[g].n = 0;
-    E->kg[g].bytes = 0;
-  }
-  if (E->A.defer || !E->A.graveyard.empty()) {  // an exchange a failed run left mid-way: its deferred frees
-    for (hipStream_t q : {E->st, E->st2, E->stc, E->ste, E->stg})  // (nothing still reads them)
-      if (q) (void)hipStreamSynchronize(q);
-    E->A.defer = false;
-    E->A.flush();
-  }
-  double T0 = now_ms();
-  bool apply_linear = !fl->flag_s;
-  uint64_t no_rounds = fl->no_rounds;
-  Arena &A = E->A;
-  int *d_err = A.get<int>("err", 1);
-  HC(hipMemsetAsync(d_err, 0, 4, st));
-
-  // forbidden bitmap, deleted, scratch defaults
-  uint8_t *d_forb = A.get<uint8_t>("forb", S);
-  uint8_t *d_deleted = A.get<uint8_t>("deleted", S);
-  HC(hipMemsetAsync(d_forb, 0, S, st));
-  HC(hipMemsetAsync(d_deleted, 0, S, st));
-  {
-    uint32_t *d_fl = A.get<uint32_t>("forb.list", E->forbidden.size());
-    h2d(E, d_fl, E->forbidden.data(), 4 * E->forbidden.size());
-    launch(st, k_mark_list, E->forbidden.size(), (const uint32_t *)d_fl, (uint64_t)E->forbidden.size(), d_forb);
-  }
-  for (const char *nm : {"el.holder_idx", "el.occ", "el.noov", "el.rep_pos"})
-    HC(hipMemsetAsync(A.get<int32_t>(nm, S), 0xff, 4 * S, st));
-  HC(hipMemsetAsync(A.get<uint8_t>("el.del", S), 0, S, st));
-  int32_t *sub_of = A.get<int32_t>("sub_of", S);
-  HC(hipMemsetAsync(sub_of, 0xff, 4 * S, st));
-
-  LcHeap lc;  // lconst (device)
-  snap_join(E);
-  E->snap_on = false;
-  E->lc_snap_n = 0;
-  E->csr_ready = false;
-  E->log_on = fl->emit_substitution_log != 0;
-  E->log_from.clear();
-  E->log_key.clear();
-  E->log_val.clear();
-  E->log_ptr.assign(1, 0);
-
-  // ======================= eq_simplification (:198-251) + renaming of linear / cons_eq rows
-  load_wait(E, 0);
-  int32_t *eq_rep = A.get<int32_t>("eq_rep", S);
-  HC(hipMemsetAsync(eq_rep, 0xff, 4 * S, st));
-  {
-    uint32_t *uf = A.get<uint32_t>("uf", S);
-    uint32_t *cnt = A.get<uint32_t>("eq.cnt", S);
-    int32_t *maxrow = A.get<int32_t>("eq.maxrow", S);
-    uint32_t *minf = A.get<uint32_t>("eq.minf", S);
-    uint32_t *minr = A.get<uint32_t>("eq.minr", S);
-    uint8_t *in_eq = A.get<uint8_t>("eq.in", S);
-    uint32_t *bf = A.get<uint32_t>("eq.bf", E->eq.n);
-    uint32_t *bfn = A.get<uint32_t>("eq.bfn", 1);
-    launch(st, k_iota_u32, S, uf, S);
-    HC(hipMemsetAsync(cnt, 0, 4 * S, st));
-    HC(hipMemsetAsync(maxrow, 0xff, 4 * S, st));
-    HC(hipMemsetAsync(minf, 0xff, 4 * S, st));
-    HC(hipMemsetAsync(minr, 0xff, 4 * S, st));
-    HC(hipMemsetAsync(in_eq, 0, S, st));
-    HC(hipMemsetAsync(bfn, 0, 4, st));
-    if (E->eq.n) {
-      launch(st, k_eq_union, E->eq.n, (const uint64_t *)E->eq.ptr, (const uint32_t *)E->eq.key, E->eq.n, uf, d_err);
-      launch(st, k_eq_stats, E->eq.n, (const uint64_t *)E->eq.ptr, (const uint32_t *)E->eq.key, E->eq.n, uf,
-             (const uint8_t *)d_forb, cnt, maxrow, minf, minr, in_eq);
-      launch(st, k_eq_assign, E->eq.n, (const uint64_t *)E->eq.ptr, (const uint32_t *)E->eq.key, E->eq.n, uf,
-             (const uint8_t *)d_forb, (const uint32_t *)minf, (const uint32_t *)minr, eq_rep, d_deleted, bf, bfn);
-    }
-    if (E->log_on && E->eq.n) {  // log_substitutions (:249)
-      uint64_t *lk = A.get<uint64_t>("lg.eqk", S), *lk2 = A.get<uint64_t>("lg.eqk2", S);
-      uint32_t *lr = A.get<uint32_t>("lg.eqr", S), *lr2 = A.get<uint32_t>("lg.eqr2", S);
-      unsigned long long *ln = A.get<unsigned long long>("lg.eqn", 1);
-      HC(hipMemsetAsync(ln, 0, 8, st));
-      launch(st, k_eq_log_keys, S, (const int32_t *)eq_rep, uf, (const uint32_t *)cnt, (const int32_t *)maxrow, S, lk, lr, ln);
-      unsigned long long nlog = 0;
-      HC(hipMemcpyAsync(&nlog, ln, 8, hipMemcpyDeviceToHost, st));
-      HC(hipStreamSynchronize(st));
-      sort_pairs(E, (const uint64_t *)lk, lk2, (const uint32_t *)lr, lr2, nlog, 64, "lgeq");
-      std::vector<uint64_t> hk(nlog);
-      std::vector<uint32_t> hr(nlog);
-      if (nlog) {
-        HC(hipMemcpyAsync(hk.data(), lk2, 8 * nlog, hipMemcpyDeviceToHost, st));
-        HC(hipMemcpyAsync(hr.data(), lr2, 4 * nlog, hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-      }
-      const uint64_t one[4] = {1, 0, 0, 0};
-      for (uint64_t i = 0; i < nlog; ++i) log_push(E, (uint32_t)hk[i], &hr[i], one, 1);  // Substitution::new(Signal)
-    }
-    // eq cons (forbidden-only constraints), ordered by cluster index (= max row) then signal
-    uint64_t nf = E->forbidden.size();
-    uint32_t *fl_d = A.get<uint32_t>("forb.list", nf);
-    uint32_t *g_root = A.get<uint32_t>("eq.g_root", nf);
-    HC(hipMemsetAsync(g_root, 0, 4 * nf, st));
-    launch(st, k_uf_roots, nf, uf, (const uint32_t *)fl_d, g_root, nf);
-    uint32_t nbf = 0;
-    HC(hipMemcpyAsync(&nbf, bfn, 4, hipMemcpyDeviceToHost, st));
-    HC(hipStreamSynchronize(st));
-    struct EqCon {  // a row of C: keys ascending, canonical values
-      int64_t order;
-      uint32_t f;
-      std::vector<uint32_t> k;
-      std::vector<uint64_t> v;
-    };
-    std::vector<EqCon> eqc;
-    // per forbidden signal: in an eq cluster?  cluster size, min forbidden, max row (one gather)
-    std::vector<uint32_t> finfo(4 * nf);
-    if (nf) {
-      uint32_t *d_fi = A.get<uint32_t>("eq.finfo", 4 * nf);
-      launch(st, k_eq_forb_info, nf, (const uint32_t *)fl_d, nf, (const uint32_t *)g_root, (const uint8_t *)in_eq,
-             (const uint32_t *)cnt, (const uint32_t *)minf, (const int32_t *)maxrow, d_fi);
-      HC(hipMemcpyAsync(finfo.data(), d_fi, 16 * nf, hipMemcpyDeviceToHost, st));
-      HC(hipStreamSynchronize(st));
-    }
-    for (uint64_t i = 0; i < nf; ++i) {
-      uint32_t f = E->forbidden[i];
-      if (!finfo[4 * i]) continue;
-      uint32_t c = finfo[4 * i + 1], mf = finfo[4 * i + 2];
-      int32_t mr = (int32_t)finfo[4 * i + 3];
-      if (c <= 1 || f == mf) continue;
-      // transform(sub(Signal f, Signal rh)) = {0: 0, rh: 1, f: -1}
-      EqCon e;
-      e.order = mr;
-      e.f = f;
-      uint64_t one[4] = {1, 0, 0, 0}, m1[4];
-      memcpy(m1, E->prime, 32);
-      m1[0] -= 1;
-      e.k = {0};
-      e.v = {0, 0, 0, 0};
-      if (mf < f) {
-        e.k.push_back(mf); e.v.insert(e.v.end(), one, one + 4);
-        e.k.push_back(f); e.v.insert(e.v.end(), m1, m1 + 4);
-      } else {
-        e.k.push_back(f); e.v.insert(e.v.end(), m1, m1 + 4);
-        e.k.push_back(mf); e.v.insert(e.v.end(), one, one + 4);
-      }
-      eqc.push_back(std::move(e));
-    }
-    if (nbf) {  // rows with both ends forbidden: kept as is when they are a cluster of their own
-      std::vector<uint64_t> rec(11 * (uint64_t)nbf);
-      uint64_t *d_rec = A.get<uint64_t>("eq.bfrec", 11 * (uint64_t)nbf);
-      // staged load: the eq values were never uploaded; these rows take theirs from the host input
-      launch(st, k_eq_bf_info, nbf, (const uint32_t *)bf, (uint64_t)nbf, (const uint64_t *)E->eq.ptr,
-             (const uint32_t *)E->eq.key, E->hin ? (const Fe *)nullptr : (const Fe *)E->eq.val, (const uint32_t *)uf,
-             (const uint32_t *)cnt, d_rec);
-      HC(hipMemcpyAsync(rec.data(), d_rec, 88 * (uint64_t)nbf, hipMemcpyDeviceToHost, st));
-      HC(hipStreamSynchronize(st));
-      for (uint32_t q = 0; q < nbf; ++q) {
-        uint64_t *x = &rec[11 * (uint64_t)q];
-        if (x[2] != 1) continue;  // a single-constraint cluster with both ends forbidden: kept as is
-        if (E->hin) {
-          const rs_lc &H = E->hin->eq;
-          const uint64_t p0 = H.ptr[x[0]];
-          for (int t = 0; t < 4; ++t) { x[3 + t] = H.val[4 * p0 + t]; x[7 + t] = H.val[4 * (p0 + 1) + t]; }
-          for (int e2 = 0; e2 < 2; ++e2) {
-            const uint64_t *v = x + 3 + 4 * e2;
-            if ((v[0] | v[1] | v[2] | v[3]) == 0 || geq4(v, E->prime))
-              throw RsError(RS_E_INVALID, "eq block: zero or non-canonical value");
-          }
-          if ((uint32_t)x[1] > (uint32_t)(x[1] >> 32)) {  // the device sorted rows; these are as given
-            x[1] = (x[1] << 32) | (x[1] >> 32);
-            for (int t = 0; t < 4; ++t) std::swap(x[3 + t], x[7 + t]);
-          }
-        }
-        EqCon e;
-        e.order = (int64_t)x[0];
-        e.f = 0;
-        e.k = {(uint32_t)x[1], (uint32_t)(x[1] >> 32)};
-        e.v.assign(x + 3, x + 11);
-        eqc.push_back(std::move(e));
-      }
-    }
-    std::sort(eqc.begin(), eqc.end(), [](const EqCon &x, const EqCon &y) {
-      return x.order != y.order ? x.order < y.order : x.f < y.f;
-    });
-    if (!eqc.empty()) {  // to the device (canonical -> Montgomery), then into the lconst heap
-      const uint64_t ne = eqc.size();
-      std::vector<uint64_t> ho(ne);
-      std::vector<uint32_t> hl(ne), hk;
-      std::vector<uint64_t> hv;
-      for (uint64_t i = 0; i < ne; ++i) {
-        ho[i] = hk.size();
-        hl[i] = (uint32_t)eqc[i].k.size();
-        hk.insert(hk.end(), eqc[i].k.begin(), eqc[i].k.end());
-        hv.insert(hv.end(), eqc[i].v.begin(), eqc[i].v.end());
-      }
-      DRows src{};
-      src.n = ne;
-      src.off = A.get<uint64_t>("lc.eo", ne);
-      src.len = A.get<uint32_t>("lc.el", ne);
-      src.key = A.get<uint32_t>("lc.ek", hk.size());
-      src.val = A.get<Fe>("lc.ev", hk.size());
-      h2d(E, src.off, ho.data(), 8 * ne);
-      h2d(E, src.len, hl.data(), 4 * ne);
-      h2d(E, src.key, hk.data(), 4 * hk.size());
-      h2d(E, src.val, hv.data(), 8 * hv.size());
-      launch(st, k_to_mont, hk.size(), E->F, (const Fe *)src.val, src.val, (uint64_t)hk.size());
-      lc.append(E, src, nullptr, ne);
-    }
-  }
-
-  // working copies (Montgomery): cons_eq (C), linear (C, one spare slot per row)
-  DRows ce{}, lin{};
-  ce.n = E->ce.n;
-  ce.off = A.get<uint64_t>("ce.off", ce.n);
-  ce.len = A.get<uint32_t>("ce.len", ce.n);
-  ce.key = A.get<uint32_t>("ce.key", E->ce.nnz);
-  ce.val = A.get<Fe>("ce.val", E->ce.nnz);
-  // kg[1]'s algorithmic bytes: k_make_ragged reads the CSR and writes the ragged copy, 72 B an entry
-  // and 20 a row; the linear rows' frames read what they rewrite (+ eq_rep / ce_has per entry)
-  KGroup &kg1 = E->kg[1];
-  if (ce.n)
-    kg1.run(st, 72 * E->ce.nnz + 20 * ce.n + 8, [&] {
-      launch(st, k_make_ragged, ce.n, E->F, (const uint64_t *)E->ce.ptr, (const uint32_t *)E->ce.key, (const Fe *)E->ce.val, ce.n,
-             (uint64_t)0, ce.off, ce.len, ce.key, ce.val);
-    });
-  lin.n = E->lin.n;
-  lin.off = A.get<uint64_t>("lin.off", lin.n);
-  lin.len = A.get<uint32_t>("lin.len", lin.n);
-  lin.key = A.get<uint32_t>("lin.key", E->lin.nnz + lin.n);
-  lin.val = A.get<Fe>("lin.val", E->lin.nnz + lin.n);
-  if (ce.n) launch(st, k_rename_rows, ce.n, E->F, ce, (const int32_t *)eq_rep);
-  if (E->log_on && ce.n) {  // log_substitutions (:271), row order
-    uint32_t *lsig = A.get<uint32_t>("lg.cesig", ce.n);
-    uint64_t *lval = A.get<uint64_t>("lg.ceval", 4 * ce.n);
-    launch(st, k_const_log, ce.n, E->F, ce, (const uint8_t *)d_forb, lsig, lval);
-    std::vector<uint32_t> hs(ce.n);
-    std::vector<uint64_t> hv(4 * ce.n);
-    HC(hipMemcpyAsync(hs.data(), lsig, 4 * ce.n, hipMemcpyDeviceToHost, st));
-    HC(hipMemcpyAsync(hv.data(), lval, 32 * ce.n, hipMemcpyDeviceToHost, st));
-    HC(hipStreamSynchronize(st));
-    const uint32_t k0 = 0;
-    for (uint64_t r = 0; r < ce.n; ++r)
-      if (hs[r] != RS_NONE) log_push(E, hs[r], &k0, &hv[4 * r], is_zero4(&hv[4 * r]) ? 0 : 1);
-  }
-
-  // ======================= constant_eq_simplification (:253-273)
-  int32_t *ce_last = A.get<int32_t>("ce.last", S);
-  uint8_t *ce_has = A.get<uint8_t>("ce.has", S);
-  Fe *ce_val = A.get<Fe>("ce.val_s", S);
-  HC(hipMemsetAsync(ce_last, 0xff, 4 * S, st));
-  HC(hipMemsetAsync(ce_has, 0, S, st));
-  {
-    uint32_t *cl = A.get<uint32_t>("ce.cons", ce.n);
-    uint32_t *cn = A.get<uint32_t>("ce.consn", 1);
-    HC(hipMemsetAsync(cn, 0, 4, st));
-    if (ce.n) {
-      launch(st, k_const_pick, ce.n, ce, (const uint8_t *)d_forb, ce_last, d_deleted, cl, cn, d_err);
-      launch(st, k_const_value, ce.n, E->F, ce, (const uint8_t *)d_forb, (const int32_t *)ce_last, ce_val, ce_has);
-    }
-    uint32_t ncons = 0;
-    HC(hipMemcpyAsync(&ncons, cn, 4, hipMemcpyDeviceToHost, st));
-    HC(hipStreamSynchronize(st));
-    if (ncons) {  // the kept rows in row order (k_const_pick listed them in any order)
-      uint32_t *sorted = A.get<uint32_t>("ce.cons_sorted", ncons);
-      sort_keys(E, (const uint32_t *)cl, sorted, ncons, 32, "ce");
-      lc.append(E, ce, sorted, ncons);
-    }
-  }
-  // the linear rows: keys first when their values are still on the way (staged load, sorted rows,
-  // no renaming collision) -- build_clusters needs keys only; the values follow in
-  // `linear_values`, run just before the elimination reads them
-  bool keys_first = false;
-  load_wait(E, 1);
-  uint8_t *lin_fixed = nullptr;
-  if (E->staged && apply_linear && lin.n && !E->h_vflag[8]) {
-    // rows that keys alone cannot settle (a renaming collision, or no non-constant key left) take
-    // their values from the host input now (hundreds of rows out of millions, typically); the rest
-    // wait for their values
-    const uint64_t unc_cap = std::max<uint64_t>(1024, lin.n / 16);
-    int *unc = A.get<int>("lin.unc", 1);
-    uint32_t *unc_list = A.get<uint32_t>("lin.unc_list", unc_cap);
-    lin_fixed = A.get<uint8_t>("lin.fixed", lin.n);
-    HC(hipMemsetAsync(unc, 0, 4, st));
-    HC(hipMemsetAsync(lin_fixed, 0, lin.n, st));
-    kg1.run(st, 13 * E->lin.nnz + 20 * lin.n + 8, [&] {
-      launch(st, k_lin_keyframes, lin.n, (const uint64_t *)E->lin.ptr, (const uint32_t *)E->lin.key, lin.n, lin,
-             (const int32_t *)eq_rep, (const uint8_t *)ce_has, unc, unc_list, unc_cap);
-    });
-    int hu = 0;
-    HC(hipMemcpyAsync(&hu, unc, 4, hipMemcpyDeviceToHost, st));
-    HC(hipStreamSynchronize(st));
-    keys_first = (uint64_t)hu <= unc_cap;
-    if (keys_first && hu) {
-      std::vector<uint32_t> rows(hu);
-      HC(hipMemcpyAsync(rows.data(), unc_list, 4 * (uint64_t)hu, hipMemcpyDeviceToHost, st));
-      HC(hipStreamSynchronize(st));
-      const rs_lc &H = E->hin->linear;
-      std::vector<uint64_t> hp(1, 0);
-      std::vector<uint32_t> hk;
-      std::vector<uint64_t> hv;
-      for (uint32_t r : rows) {
-        const uint64_t b = H.ptr[r], e = H.ptr[r + 1];
-        hk.insert(hk.end(), H.col + b, H.col + e);
-        hv.insert(hv.end(), H.val + 4 * b, H.val + 4 * e);
-        hp.push_back(hk.size());
-      }
-      uint64_t *d_hp = A.get<uint64_t>("lin.fx_ptr", hp.size());
-      uint32_t *d_hk = A.get<uint32_t>("lin.fx_key", std::max<size_t>(hk.size(), 1));
-      Fe *d_hv = A.get<Fe>("lin.fx_val", std::max<size_t>(hk.size(), 1));
-      uint32_t *d_rows = A.get<uint32_t>("lin.fx_rows", hu);
-      h2d(E, d_hp, hp.data(), 8 * hp.size());
-      h2d(E, d_hk, hk.data(), 4 * hk.size());
-      h2d(E, d_hv, hv.data(), 8 * hv.size());
-      h2d(E, d_rows, rows.data(), 4 * rows.size());
-      launch(st, k_lin_fixrows, (uint64_t)hu, E->F, (const uint64_t *)d_hp, (const uint32_t *)d_hk, (const Fe *)d_hv,
-             (const uint32_t *)d_rows, (uint64_t)hu, lin, (const int32_t *)eq_rep, (const uint8_t *)ce_has,
-             (const Fe *)ce_val, lin_fixed);
-    }
-    if (g_prof_env) fprintf(stderr, "[rs-prof] keys-first: %d rows settled from host values\n", hu);
-  }
-  if (!keys_first) {
-    load_wait(E, 2);
-    if (lin.n) {
-      kg1.run(st, 72 * E->lin.nnz + 20 * lin.n + 8 + 77 * E->lin.nnz + 16 * lin.n, [&] {
-        launch(st, k_make_ragged, lin.n, E->F, (const uint64_t *)E->lin.ptr, (const uint32_t *)E->lin.key, (const Fe *)E->lin.val,
-               lin.n, (uint64_t)1, lin.off, lin.len, lin.key, lin.val);
-        launch(st, k_linear_frames12, lin.n, E->F, lin, (const int32_t *)eq_rep, (const uint8_t *)ce_has, (const Fe *)ce_val);
-      });
-    }
-  }
-  const std::function<void()> linear_values = [&]() {
-    load_wait(E, 2);
-    kg1.run(st, 77 * E->lin.nnz + 20 * lin.n + 8, [&] {
-      launch(st, k_lin_valframes, lin.n, E->F, (const uint64_t *)E->lin.ptr, (const uint32_t *)E->lin.key, (const Fe *)E->lin.val,
-             lin.n, lin, (const int32_t *)eq_rep, (const uint8_t *)ce_has, (const Fe *)ce_val, (const uint8_t *)lin_fixed);
-    });
-  };
-  if (g_prof_env) fprintf(stderr, "[rs-prof] linear rows: %s\n", keys_first ? "keys first" : "keys + values");
-  HC(hipStreamSynchronize(st));
-  E->stats.eq_ms = now_ms() - T0;
-
-  // ======================= obtain_and_simplify_non_linear (non_linear_utils.rs:6-31): setup
-  const uint64_t n_nl = E->na.n;
-  DRows ia{}, ib{}, ic{};
-  auto mk_in = [&](rs_engine::Blk &B, DRows &R, const char *nm, hipStream_t ms) {
-    R.n = B.n;
-    R.off = A.get<uint64_t>(std::string(nm) + ".off", R.n);
-    R.len = A.get<uint32_t>(std::string(nm) + ".len", R.n);
-    R.key = A.get<uint32_t>(std::string(nm) + ".key", B.nnz);
-    R.val = A.get<Fe>(std::string(nm) + ".val", B.nnz);
-    if (R.n)
-      kg1.run(ms, 72 * B.nnz + 20 * R.n + 8, [&] {
-        launch(ms, k_make_ragged, R.n, E->F, (const uint64_t *)B.ptr, (const uint32_t *)B.key, (const Fe *)B.val, R.n, (uint64_t)0,
-               R.off, R.len, R.key, R.val);
-      });
-  };
-  // the non-linear blocks are staged where the frames first need them: their upload (group 2)
-  // overlaps the clustering and elimination
-  bool nl_staged = false;
-  auto stage_nl = [&]() {
-    if (nl_staged) return;
-    load_wait(E, 3);
-    // the conversion on the copy stream (in order after the blocks' upload and checks), beside what
-    // the main stream still runs (the tail's finish): the frames wait for it there
-    static const bool on_main = getenv("RS_NLC_MAIN") != nullptr;
-    hipStream_t cs = on_main ? st : E->stc;
-    mk_in(E->na, ia, "nla", cs);
-    mk_in(E->nb, ib, "nlb", cs);
-    mk_in(E->nc, ic, "nlc", cs);
-    HC(hipEventRecord(E->ev_nlc, cs));
-    HC(hipStreamWaitEvent(st, E->ev_nlc, 0));
-    nl_staged = true;
-  };
-  // storage rows live in one growable heap of (key, value) entries, owned by the engine
-  DRows sa{}, sb{}, sc{};
-  uint64_t heap_top = 0;
-  uint32_t *heap_k = E->heap_k;
-  Fe *heap_v = E->heap_v;
-  auto heap_reserve = [&](uint64_t need) {
-    if (heap_top + need <= E->heap_cap && E->heap_k) return;
-    // grows by a quarter (doubling left the 20 M-row circuit's heap at 12 GB for 6 GB of rows; eight
-    // in-process ranks on one GPU did not fit)
-    uint64_t ncap = std::max<uint64_t>(heap_top + need + (heap_top + need) / 16, E->heap_cap + E->heap_cap / 4);
-    ncap = std::max<uint64_t>(ncap, 1 << 16);
-    uint32_t *nk = nullptr;
-    Fe *nv = nullptr;
-    HC(hipStreamSynchronize(st));
-    HC(hipMalloc((void **)&nk, 4 * ncap));
-    HC(hipMalloc((void **)&nv, 32 * ncap));
-    if (heap_top) {
-      HC(hipMemcpyAsync(nk, E->heap_k, 4 * heap_top, hipMemcpyDeviceToDevice, st));
-      HC(hipMemcpyAsync(nv, E->heap_v, 32 * heap_top, hipMemcpyDeviceToDevice, st));
-      HC(hipStreamSynchronize(st));
-    }
-    if (E->snap_on) HC(hipStreamSynchronize(E->stc));  // the early gather reads the old heap
-    if (E->heap_k) { HC(hipFree(E->heap_k)); HC(hipFree(E->heap_v)); }
-    E->heap_k = heap_k = nk;
-    E->heap_v = heap_v = nv;
-    E->heap_cap = ncap;
-  };
-  unsigned long long *d_bytes = A.get<unsigned long long>("nl.bytes", 1);
-  HC(hipMemsetAsync(d_bytes, 0, 8, st));
-  int *d_fw_err = A.get<int>("fw.err", 1);  // k_frames_wave batch bounds (checked with the input checks)
-  HC(hipMemsetAsync(d_fw_err, 0, 4, st));
-  FrameArgs fr;
-  fr.F = E->F;
-  fr.eq_rep = eq_rep;
-  fr.ce_has = ce_has;
-  fr.ce_val = ce_val;
-  fr.sub_of = sub_of;
-  for (DRows *R : {&sa, &sb, &sc}) {
-    R->n = n_nl;
-  }
-  sa.off = A.get<uint64_t>("st.a.off", n_nl);
-  sa.len = A.get<uint32_t>("st.a.len", n_nl);
-  sb.off = A.get<uint64_t>("st.b.off", n_nl);
-  sb.len = A.get<uint32_t>("st.b.len", n_nl);
-  sc.off = A.get<uint64_t>("st.c.off", n_nl);
-  sc.len = A.get<uint32_t>("st.c.len", n_nl);
-  uint64_t *ca = nullptr, *cb = nullptr, *cc = nullptr;
-  U3 *cap3 = nullptr, *sc3 = nullptr;
-  uint64_t *nl_late = nullptr, *nl_lpos = nullptr;
-  uint8_t *hmark = nullptr;
-  uint32_t *nl_lids = nullptr;
-  uint64_t n_late = 0;
-  if (n_nl) {
-    ca = A.get<uint64_t>("nl.capa", n_nl); cb = A.get<uint64_t>("nl.capb", n_nl); cc = A.get<uint64_t>("nl.capc", n_nl);
-    cap3 = A.get<U3>("nl.c3", n_nl); sc3 = A.get<U3>("nl.s3", n_nl);
-  }
-  // one pass of the frames over the non-linear rows ids[0, n) (phase: see NLArgs); the fill's
-  // kernel time is read from (e0, e1) once the caller synchronises
-  // streamed result (output.hpp): the non-linear rows round 1's substitution has finished and left
-  // non-linear (storage rows) are gathered to the early region and copied to the host on the copy
-  // stream while the run goes on.  late: rows a second frames pass still has to do (nullptr: none).
-  uint8_t *so_early = nullptr;
-  U3 *so_eoff = nullptr;
-  bool fh_split = false;  // the last nl_phase ran in two halves (ev_fh)
-  // hi_rows < n_nl: the first pass's first half only (snap_take_h2 takes the rest once it is done)
-  auto snap_take = [&](const uint64_t *late, uint64_t hi_rows) {
-    if (!E->stream_out || !n_nl) return;
-    so_early = A.get<uint8_t>("so.early", n_nl);
-    so_eoff = A.get<U3>("so.eoff", n_nl);
-    U3 *elen = A.get<U3>("so.elen", n_nl);
-    Comm *CM = E->comm.get();
-    const bool shard = CM && CM->world > 1;
-    // the gather reads copies of the selected rows' views: the second pass and later rounds re-point rows
-    const DRows *src[3] = {&sa, &sb, &sc};
-    const char *nm[3] = {"so.a", "so.b", "so.c"};
-    DRows cp[3];
-    ViewCopy vc;
-    for (int q = 0; q < 3; ++q) {
-      cp[q] = *src[q];
-      cp[q].off = vc.off[q] = A.get<uint64_t>(std::string(nm[q]) + ".off", n_nl);
-      cp[q].len = vc.len[q] = A.get<uint32_t>(std::string(nm[q]) + ".len", n_nl);
-    }
-    launch(st, k_snap_flags, n_nl, sa, sb, sc, late, n_nl, shard ? E->nl_lo : (uint64_t)0, shard ? E->nl_hi : hi_rows, so_early, elen,
-           vc);
-    const U3 et = excl_scan_u3(E, elen, so_eoff, n_nl, "so");
-    // single engine: the lconst rows so far (final as they enter the heap) go behind the C part
-    E->lc_snap_n = shard ? 0 : lc.n;
-    E->lc_snap_base = et.c;
-    const uint64_t lc_e = shard ? 0 : lc.top;
-    const uint64_t ev[3] = {et.a, et.b, et.c + lc_e};
-    E->sh_full = false;
-    if (shard) {  // every rank's share of each part gets the same capacity in the shared region
-      for (int q = 0; q < 3; ++q) E->sh_cap[q] = CM->max_u64(std::max<uint64_t>(ev[q] + ev[q] / 4 + 65536, E->sh_cap[q]), st);
-      E->sh_ent = CM->shared_host(0, sh_ent_bytes(E), st);
-      if (!E->sh_ent) {  // every rank alike (shared_host agrees): no stream; each rank fetches the whole result
-        if (g_prof_env) fprintf(stderr, "[rs-prof] no shared host memory: unstreamed per-rank result\n");
-        E->stream_out = false;
-        return;
-      }
-    }
-    HC(hipEventRecord(E->ev_snap0, st));
-    HC(hipStreamWaitEvent(E->stc, E->ev_snap0, 0));
-    for (int q = 0; q < 3; ++q) {
-      E->snap_e[q] = ev[q];
-      E->snap_hint[q] = std::max(E->snap_hint[q], ev[q]);
-      // the device early region = the head of the layout's arrays; the late rows follow it
-      // room for the second snapshot's rows too (the largest early region so far, else a margin)
-      // (a first half: room for the whole pass, scaled by rows)
-      const uint64_t est = hi_rows < n_nl && hi_rows ? (uint64_t)((double)ev[q] * n_nl / hi_rows) : ev[q];
-      const uint64_t cap = std::max<uint64_t>(est + std::max<uint64_t>(est / 4, 1 << 16), E->snap_hint[q]);
-      const std::string xn = std::string("out.") + "abc"[q];
-      uint32_t *col = A.get<uint32_t>(xn + ".xcol", cap);
-      uint64_t *val = A.get<uint64_t>(xn + ".xval", 4 * cap);
-      // kg[2]'s algorithmic bytes: 72 an entry (key + value read, canonical key + value written) and
-      // what a row's selection reads (its flag; its extent when selected)
-      if (ev[q])
-        E->kg[2].run(E->stc, 13 * n_nl + 72 * ev[q], [&] {
-          launch(E->stc, k_snap_gather, n_nl, E->F, cp[q], (const uint8_t *)so_early, (const U3 *)so_eoff, q, n_nl, col, val,
-                 (const uint64_t *)nullptr, (uint64_t)0);
-        });
-      if (q == 2 && lc_e) {
-        const DRows lcv = lc.view(A);
-        E->kg[2].run(E->stc, 72 * lc_e, [&] {
-          launch(E->stc, k_lc_snap, lc_e, E->F, (const uint32_t *)lcv.key, (const Fe *)lcv.val, lc_e, col + et.c, val + 4 * et.c);
-        });
-      }
-      void *hc = shard ? (void *)(sh_col(E, q) + CM->rank * E->sh_cap[q]) : pin_get(E, 3 + q, 4 * cap);
-      void *hv = shard ? (void *)(sh_val(E, q) + 4 * CM->rank * E->sh_cap[q]) : pin_get(E, 6 + q, 32 * cap);
-      E->snap_cap[q] = cap;
-      E->snap_host[2 * q] = hc;
-      E->snap_host[2 * q + 1] = hv;
-      if (ev[q]) {  // a part's copies start once its own gather is done
-        HC(hipEventRecord(E->ev_snapq[q], E->stc));
-        snap_push(E, {hc, col, 4 * ev[q], E->ev_snapq[q]});
-        snap_push(E, {hv, val, 32 * ev[q], E->ev_snapq[q]});
-      }
-    }
-    HC(hipEventRecord(E->ev_snap, E->stc));
-    E->snap_on = true;
-    if (g_prof_env)
-      fprintf(stderr, "[rs-prof] stream: early region %llu / %llu / %llu entries (%.1f MB)%s\n", (unsigned long long)ev[0],
-              (unsigned long long)ev[1], (unsigned long long)ev[2], 36e-6 * (ev[0] + ev[1] + ev[2]), late ? " after the first pass" : "");
-  };
-  // The second snapshot (single engine): the rows of the second frames pass -- those touching the head
-  // clusters -- that stayed storage rows go behind the first snapshot's, when they fit the regions
-  // sized at the first (else they stay late), so they stream during the later rounds too.
-  auto snap_take2 = [&]() {
-    if (!E->snap_on || !nl_late || !n_late || (E->comm && E->comm->world > 1)) return;
-    HC(hipStreamWaitEvent(st, E->ev_snap, 0));  // the first snapshot's gathers read the flags rewritten here
-    U3 *elen = A.get<U3>("so.elen", n_nl), *eoff2 = A.get<U3>("so.eoff2", n_nl);
-    const DRows *src[3] = {&sa, &sb, &sc};
-    const char *nm[3] = {"so2.a", "so2.b", "so2.c"};
-    DRows cp[3];  // copies of the selected rows' views (the rounds re-point rows)
-    ViewCopy vc;
-    for (int q = 0; q < 3; ++q) {
-      cp[q] = *src[q];
-      cp[q].off = vc.off[q] = A.get<uint64_t>(std::string(nm[q]) + ".off", n_nl);
-      cp[q].len = vc.len[q] = A.get<uint32_t>(std::string(nm[q]) + ".len", n_nl);
-    }
-    launch(st, k_snap_lens2, n_nl, sa, sb, sc, (const uint64_t *)nl_late, n_nl, elen, vc);
-    const U3 et = excl_scan_u3(E, elen, eoff2, n_nl, "so2");
-    const uint64_t e2[3] = {et.a, et.b, et.c};
-    for (int q = 0; q < 3; ++q) E->snap_hint[q] = std::max(E->snap_hint[q], E->snap_e[q] + e2[q]);
-    for (int q = 0; q < 3; ++q)
-      if (E->snap_e[q] + e2[q] > E->snap_cap[q]) return;  // no room this time (the hint grows the next run's)
-    launch(st, k_snap_mark2, n_nl, (const uint64_t *)nl_late, (const U3 *)elen, (const U3 *)eoff2,
-           U3{E->snap_e[0], E->snap_e[1], E->snap_e[2]}, n_nl, so_early, so_eoff);
-    HC(hipEventRecord(E->ev_snap0, st));
-    HC(hipStreamWaitEvent(E->stc, E->ev_snap0, 0));
-    for (int q = 0; q < 3; ++q) {
-      const uint64_t b = E->snap_e[q];
-      const std::string xn = std::string("out.") + "abc"[q];
-      uint32_t *col = A.get<uint32_t>(xn + ".xcol", 1);
-      uint64_t *val = A.get<uint64_t>(xn + ".xval", 1);
-      if (!e2[q]) continue;
-      E->kg[2].run(E->stc, 21 * n_nl + 72 * e2[q], [&] {
-        launch(E->stc, k_snap_gather, n_nl, E->F, cp[q], (const uint8_t *)so_early, (const U3 *)so_eoff, q, n_nl, col, val,
-               (const uint64_t *)nl_late, (uint64_t)0);
-      });
-      HC(hipEventRecord(E->ev_snapq[3 + q], E->stc));
-      snap_push(E, {(uint32_t *)E->snap_host[2 * q] + b, col + b, 4 * e2[q], E->ev_snapq[3 + q]});
-      snap_push(E, {(uint64_t *)E->snap_host[2 * q + 1] + 4 * b, val + 4 * b, 32 * e2[q], E->ev_snapq[3 + q]});
-      E->snap_e[q] = b + e2[q];
-    }
-    HC(hipEventRecord(E->ev_snap, E->stc));
-    if (g_prof_env)
-      fprintf(stderr, "[rs-prof] stream: second snapshot %llu / %llu / %llu entries (%.1f MB)\n", (unsigned long long)e2[0],
-              (unsigned long long)e2[1], (unsigned long long)e2[2], 36e-6 * (e2[0] + e2[1] + e2[2]));
-  };
-  // split < n (phase 1): the frames of rows [0, split), `between` (the first half's snapshot), then the
-  // rest; the kernel time excludes what runs between
-  // The first pass's second half (single engine): its rows [h, n_nl) that are done and stayed storage
-  // rows go behind the first half's in the regions sized at the first snapshot, when they fit (else
-  // they stay late and the capacity hint grows).
-  auto snap_take_h2 = [&](uint64_t h) {
-    if (!E->snap_on || (E->comm && E->comm->world > 1)) return;
-    HC(hipStreamWaitEvent(st, E->ev_snap, 0));  // the first half's gathers read the flags rewritten here
-    U3 *elen = A.get<U3>("so.elenh", n_nl), *eoffh = A.get<U3>("so.eoffh", n_nl);
-    const DRows *src[3] = {&sa, &sb, &sc};
-    const char *nm[3] = {"soh.a", "soh.b", "soh.c"};
-    DRows cp[3];  // copies of the selected rows' views (the second pass and the rounds re-point rows)
-    ViewCopy vc;
-    for (int q = 0; q < 3; ++q) {
-      cp[q] = *src[q];
-      cp[q].off = vc.off[q] = A.get<uint64_t>(std::string(nm[q]) + ".off", n_nl);
-      cp[q].len = vc.len[q] = A.get<uint32_t>(std::string(nm[q]) + ".len", n_nl);
-    }
-    launch(st, k_snap_lens_rng, n_nl, sa, sb, sc, (const uint64_t *)nl_late, h, n_nl, n_nl, elen, vc);
-    const U3 et = excl_scan_u3(E, elen, eoffh, n_nl, "soh");
-    const uint64_t e2[3] = {et.a, et.b, et.c};
-    for (int q = 0; q < 3; ++q) E->snap_hint[q] = std::max(E->snap_hint[q], E->snap_e[q] + e2[q]);
-    for (int q = 0; q < 3; ++q)
-      if (E->snap_e[q] + e2[q] > E->snap_cap[q]) return;
-    launch(st, k_snap_mark_sel, n_nl, (const U3 *)elen, (const U3 *)eoffh, U3{E->snap_e[0], E->snap_e[1], E->snap_e[2]}, n_nl,
-           so_early, so_eoff);
-    HC(hipEventRecord(E->ev_snap0, st));
-    HC(hipStreamWaitEvent(E->stc, E->ev_snap0, 0));
-    for (int q = 0; q < 3; ++q) {
-      const uint64_t b = E->snap_e[q];
-      const std::string xn = std::string("out.") + "abc"[q];
-      uint32_t *col = A.get<uint32_t>(xn + ".xcol", 1);
-      uint64_t *val = A.get<uint64_t>(xn + ".xval", 1);
-      if (!e2[q]) continue;
-      E->kg[2].run(E->stc, 13 * (n_nl - h) + 72 * e2[q], [&] {
-        launch(E->stc, k_snap_gather, n_nl - h, E->F, cp[q], (const uint8_t *)so_early, (const U3 *)so_eoff, q, n_nl, col, val,
-               (const uint64_t *)nullptr, h);
-      });
-      HC(hipEventRecord(E->ev_snaph[q], E->stc));
-      snap_push(E, {(uint32_t *)E->snap_host[2 * q] + b, col + b, 4 * e2[q], E->ev_snaph[q]});
-      snap_push(E, {(uint64_t *)E->snap_host[2 * q + 1] + 4 * b, val + 4 * b, 32 * e2[q], E->ev_snaph[q]});
-      E->snap_e[q] = b + e2[q];
-    }
-    HC(hipEventRecord(E->ev_snap, E->stc));
-    if (g_prof_env)
-      fprintf(stderr, "[rs-prof] stream: the first pass's second half %llu / %llu / %llu entries (%.1f MB)\n", (unsigned long long)e2[0],
-              (unsigned long long)e2[1], (unsigned long long)e2[2], 36e-6 * (e2[0] + e2[1] + e2[2]));
-  };
-  auto nl_phase = [&](int phase, const uint32_t *ids, uint64_t n, hipEvent_t e0, hipEvent_t e1, uint64_t split = ~0ull,
-                      const std::function<void()> &between = {}) {
-    stage_nl();
-    NLArgs a{};
-    a.fr = fr;
-    a.a = ia; a.b = ib; a.c = ic;
-    a.cap_a = ca; a.cap_b = cb; a.cap_c = cc;
-    a.bytes = d_bytes;
-    a.ids = ids;
-    a.n = n;
-    a.phase = phase;
-    a.hmark = hmark;
-    a.late = nl_late;
-    launch(st, k_nl_count, n, a);
-    const bool lists = phase == 1 && n_nl;
-    if (lists) {  // the skipped rows, listed for the second pass (their count comes back with the heap's)
-      dev_scan_u64(E, nl_late, nl_lpos, n_nl, st, "nll");
-      launch(st, k_scatter_ids, n_nl, (const uint64_t *)nl_late, (const uint64_t *)nl_lpos, n_nl, nl_lids);
-    }
-    launch(st, k_pack3, n, (const uint64_t *)ca, (const uint64_t *)cb, (const uint64_t *)cc, n, cap3);
-    const U3 t3 = lists ? excl_scan_u3(E, cap3, sc3, n, "nl", nl_late + n_nl - 1, nl_lpos + n_nl - 1, &n_late)
-                        : excl_scan_u3(E, cap3, sc3, n, "nl");
-    if (g_prof_env) fprintf(stderr, "[rs-prof] nl phase %d: %llu rows, %llu heap entries\n", phase, (unsigned long long)n,
-                            (unsigned long long)(t3.a + t3.b + t3.c));
-    heap_reserve(t3.a + t3.b + t3.c);
-    launch(st, k_set_offsets_u3, n, (const U3 *)sc3, heap_top, heap_top + t3.a, heap_top + t3.a + t3.b, n, sa.off, sb.off,
-           sc.off, phase == 1 ? (const U3 *)cap3 : nullptr, ids);
-    heap_top += t3.a + t3.b + t3.c;
-    sa.key = sb.key = sc.key = heap_k;
-    sa.val = sb.val = sc.val = heap_v;
-    a.oa = sa; a.ob = sb; a.oc = sc;
-    // whole waves on batches of rows (frames_wave.hpp); the rows too large for a batch, one lane each
-    FrameWaveArgs w{};
-    w.fr = fr;
-    w.in[0] = ia; w.in[1] = ib; w.in[2] = ic;
-    w.out[0] = sa; w.out[1] = sb; w.out[2] = sc;
-    w.cap[0] = ca; w.cap[1] = cb; w.cap[2] = cc;
-    w.ids = ids;
-    w.n = n;
-    w.late = phase == 1 ? nl_late : nullptr;
-    w.big = A.get<uint32_t>(phase == 1 ? "nl.big1" : "nl.big2", n);
-    w.n_big = A.get<unsigned>(phase == 1 ? "nl.nbig1" : "nl.nbig2", 1);
-    w.err = d_fw_err;
-    w.bytes = d_bytes;
-    HC(hipMemsetAsync(w.n_big, 0, 4, st));
-#ifdef RS_FWCLK
-    w.clk = A.get<unsigned long long>(phase == 1 ? "fw.clk1" : "fw.clk2", 32 + 8 * 64);
-    HC(hipMemsetAsync(w.clk, 0, 8 * (32 + 8 * 64), st));
-#endif
-    a.xlist = w.big;
-    a.n_xlist = w.n_big;
-    HC(hipEventRecord(e0, st));
-    fh_split = split < n;
-    if (fh_split) {
-      w.n = split;
-      launch_capped(st, k_frames_wave<0>, split, kFwBlocks, w);
-      launch(st, k_nl_fill, n, a);  // the rows over a batch listed so far
-      HC(hipEventRecord(E->ev_fh[0], st));
-      between();
-      HC(hipMemsetAsync(w.n_big, 0, 4, st));
-      HC(hipEventRecord(E->ev_fh[1], st));
-      w.x0 = split;
-      w.n = n;
-      launch_capped(st, k_frames_wave<0>, n - split, kFwBlocks, w);
-    } else {
-      launch_capped(st, k_frames_wave<0>, n, kFwBlocks, w);
-    }
-    launch(st, k_nl_fill, n, a);  // a grid for every row: the list may be long, idle lanes leave at once
-    HC(hipEventRecord(e1, st));
-    if (g_prof_env) {
-      unsigned nb = 0;
-      HC(hipMemcpyAsync(&nb, w.n_big, 4, hipMemcpyDeviceToHost, st));
-      HC(hipStreamSynchronize(st));
-      fprintf(stderr, "[rs-prof] nl phase %d: %u rows over a wave batch\n", phase, nb);
-      if (w.clk) {
-        unsigned long long c[32 + 8 * 64];
-        HC(hipMemcpy(c, w.clk, sizeof c, hipMemcpyDeviceToHost));
-        for (int q = 0; q < 0; ++q) {
-          const unsigned long long *d = c + 32 + q * 64;
-          fprintf(stderr, "[rs-prof] zero A row %llu: %llu entries:", d[0], d[1]);
-          for (unsigned i = 0; i < d[1] && i < 6; ++i)
-            fprintf(stderr, " (key/slot %llu kind %llu w %llu)", d[2 + i] >> 32, (d[2 + i] >> 16) & 0xff, d[2 + i] & 0xffff);
-          fprintf(stderr, " | %llu terms:", d[8]);
-          for (unsigned i = 0; i < d[8] && i < 24; ++i) fprintf(stderr, " %llu:%llx", d[9 + 2 * i] >> 32, d[10 + 2 * i]);
-          fprintf(stderr, "\n");
-        }
-        fprintf(stderr, "[rs-prof] frames clocks (Mcycles summed over waves): groups %.1f entries %.1f terms %.1f rank %.1f "
-                "heads %.1f emit %.1f rows %.1f plan %.1f | batches %llu, wave total %.1f over %llu waves\n",
-                c[0] / 1e6, c[1] / 1e6, c[2] / 1e6, c[3] / 1e6, c[4] / 1e6, c[5] / 1e6, c[6] / 1e6, c[7] / 1e6, c[8],
-                c[9] / 1e6, c[10]);
-        fprintf(stderr, "[rs-prof] frames fallbacks: A const %llu, B const %llu | emit: loads %.1f values %.1f sync %.1f stores %.1f\n",
-                c[12], c[13], c[16] / 1e6, c[17] / 1e6, c[18] / 1e6, c[19] / 1e6);
-      }
-    }
-    E->stats.apply_kernel_launches++;
-  };
-  auto nl_ms = [&](hipEvent_t e0, hipEvent_t e1) {
-    float ms = 0;
-    HC(hipEventSynchronize(e1));
-    if (fh_split) {  // the two halves, without the snapshot between them
-      float m2 = 0;
-      HC(hipEventElapsedTime(&ms, e0, E->ev_fh[0]));
-      HC(hipEventElapsedTime(&m2, E->ev_fh[1], e1));
-      ms += m2;
-      fh_split = false;
-    } else {
-      HC(hipEventElapsedTime(&ms, e0, e1));
-    }
-    E->stats.apply_kernel_ms += ms;
-  };
-  // rows that touch none of the largest clusters go through the frames while those clusters are
-  // still being eliminated (sharded: after the exchange of the clusters other than the head, which every
-  // rank eliminates itself)
-  bool nl_split = false;
-  HeadOverlap overlap = [&](const uint32_t *ids, uint64_t n_head, const ElimArgs &ea) {
-    hmark = A.get<uint8_t>("nl.hmark", E->S);
-    nl_late = A.get<uint64_t>("nl.late", n_nl);
-    nl_lpos = A.get<uint64_t>("nl.lpos", n_nl);
-    nl_lids = A.get<uint32_t>("nl.lids", n_nl);
-    HC(hipMemsetAsync(hmark, 0, E->S, st));
-    hipLaunchKernelGGL(k_mark_head_keys, dim3(16, (unsigned)n_head), dim3(256), 0, st, ea.rows, (const uint32_t *)ea.perm,
-                       (const uint64_t *)ea.cl_off, ids, hmark);
-    HC(hipGetLastError());
-    fr.h_off = ea.h_off; fr.h_len = ea.h_len; fr.pk = ea.pk; fr.pv = ea.pv;
-    // the first pass in two halves with a snapshot after each (single engine, streamed): the result
-    // stream starts after half the pass
-    const bool halves = E->stream_out && !(E->comm && E->comm->world > 1) && n_nl >= (getenv("RS_HALVES_MIN") ? strtoull(getenv("RS_HALVES_MIN"), nullptr, 10) : (1ull << 20)) &&
-                       !getenv("RS_NO_HALVES");
-    const double frac = getenv("RS_HALF_FRAC") ? atof(getenv("RS_HALF_FRAC")) : 0.5;
-    const uint64_t h = halves ? std::max<uint64_t>(1, std::min<uint64_t>(n_nl - 1, (uint64_t)(n_nl * frac))) : n_nl;
-    nl_phase(1, nullptr, n_nl, E->evx[8], E->evx[9], h, [&] { snap_take(nl_late, h); });
-    if (!halves) snap_take(nl_late, n_nl);
-    else snap_take_h2(h);
-    nl_split = true;
-  };
-
-  // ======================= linear round 1 (:544-578)
-  ElimOut eo;
-  Pool P = get_pool(E, 1 << 20);
-  if (apply_linear) {
-    // sharded: only the relevant substitutions' right-hand sides travel (the log needs them all)
-    uint8_t *relevant = nullptr;
-    if (E->comm && E->comm->world > 1 && !E->log_on) {
-      relevant = A.get<uint8_t>("x.relevant", S);
-      HC(hipMemsetAsync(relevant, 0, S, st));
-      if (n_nl) {
-        stage_nl();
-        for (const DRows *R : {&ia, &ib, &ic})
-          launch(st, k_mark_relevant, R->n, *R, (const int32_t *)eq_rep, (const uint8_t *)ce_has, relevant);
-      }
-    }
-    if (E->comm && E->comm->world > 1) load_order_collectives(E);
-    run_linear_simplification(E, lin, fl->use_old_heuristics, eo, P, d_err, d_forb, sub_of, d_deleted,
-                              n_nl ? &overlap : nullptr, keys_first ? &linear_values : nullptr, relevant);
-    if (E->log_on) log_linear_round(E, eo, P);
-    collect_leftovers(E, eo, P, lc);
-    E->stats.rounds++;
-  } else {
-    // --O1: the linear rows join lconst as they are after the eq / constant frames (:575-577)
-    if (!keys_first) lc.append(E, lin, nullptr, lin.n);
-    else throw RsError(RS_E_INTERNAL, "--O1 with keys-first linear rows");
-  }
-
-  // ======================= obtain_and_simplify_non_linear (non_linear_utils.rs:6-31)
-  double Ts = now_ms();
-  fr.h_off = A.get<uint64_t>("el.h_off", 1);
-  fr.h_len = A.get<uint32_t>("el.h_len", 1);
-  fr.pk = P.pk;
-  fr.pv = P.pv;
-  if (n_nl) {
-    if (nl_split) nl_ms(E->evx[8], E->evx[9]);
-    if (!nl_split) {
-      nl_phase(0, nullptr, n_nl, E->ev0, E->ev1);
-      snap_take(nullptr, n_nl);
-      nl_ms(E->ev0, E->ev1);
-    } else if (n_late) {
-      nl_phase(2, nl_lids, n_late, E->ev0, E->ev1);
-      snap_take2();
-      nl_ms(E->ev0, E->ev1);
-    }
-  }
-  unsigned long long bytes = 0;
-  HC(hipMemcpyAsync(&bytes, d_bytes, 8, hipMemcpyDeviceToHost, st));
-  // split: storage (still non-linear) vs with_linear, both in DFS order
-  uint64_t n_st = 0, n_wl = 0;
-  uint32_t *st_ids = A.get<uint32_t>("st.ids", n_nl), *wl_ids = A.get<uint32_t>("wl.ids", n_nl);
-  if (n_nl) {
-    uint64_t *fl_lin = A.get<uint64_t>("fl.lin", n_nl), *fl_nl = A.get<uint64_t>("fl.nl", n_nl);
-    uint64_t *p_lin = A.get<uint64_t>("fl.plin", n_nl), *p_nl = A.get<uint64_t>("fl.pnl", n_nl);
-    launch(st, k_flag_linear, n_nl, (const uint32_t *)sa.len, (const uint32_t *)sb.len, n_nl, fl_lin, fl_nl);
-    n_wl = excl_scan_u64(E, fl_lin, p_lin, n_nl, "fl");
-    n_st = excl_scan_u64(E, fl_nl, p_nl, n_nl, "fn");
-    launch(st, k_scatter_ids, n_nl, (const uint64_t *)fl_lin, (const uint64_t *)p_lin, n_nl, wl_ids);
-    launch(st, k_scatter_ids, n_nl, (const uint64_t *)fl_nl, (const uint64_t *)p_nl, n_nl, st_ids);
-  }
-  HC(hipStreamSynchronize(st));
-  E->stats.apply_bytes += bytes;
-  if (no_rounds > 0) no_rounds--;
-
-  // storage view (compacted) and the non-linear signal map bitmap (:599-612)
-  DRows ta_{}, tb_{}, tc_{};
-  for (DRows *R : {&ta_, &tb_, &tc_}) { R->n = n_st; R->key = heap_k; R->val = heap_v; }
-  ta_.off = A.get<uint64_t>("sv.a.off", n_st); ta_.len = A.get<uint32_t>("sv.a.len", n_st);
-  tb_.off = A.get<uint64_t>("sv.b.off", n_st); tb_.len = A.get<uint32_t>("sv.b.len", n_st);
-  tc_.off = A.get<uint64_t>("sv.c.off", n_st); tc_.len = A.get<uint32_t>("sv.c.len", n_st);
-  if (n_st) {
-    launch(st, k_view_rows, n_st, (const uint64_t *)sa.off, (const uint32_t *)sa.len, (const uint32_t *)st_ids, n_st, ta_.off, ta_.len);
-    launch(st, k_view_rows, n_st, (const uint64_t *)sb.off, (const uint32_t *)sb.len, (const uint32_t *)st_ids, n_st, tb_.off, tb_.len);
-    launch(st, k_view_rows, n_st, (const uint64_t *)sc.off, (const uint32_t *)sc.len, (const uint32_t *)st_ids, n_st, tc_.off, tc_.len);
-  }
-  uint8_t *nlmap = A.get<uint8_t>("nlmap", S);
-  HC(hipMemsetAsync(nlmap, 0, S, st));
-  if (n_st) {
-    launch(st, k_mark_keys, n_st, ta_, nlmap);
-    launch(st, k_mark_keys, n_st, tb_, nlmap);
-    launch(st, k_mark_keys, n_st, tc_, nlmap);
-  }
-  // the current linear list: a C-only view
-  DRows lv{};
-  lv.n = n_wl;
-  lv.key = heap_k;
-  lv.val = heap_v;
-  lv.off = A.get<uint64_t>("lv.off", n_wl);
-  lv.len = A.get<uint32_t>("lv.len", n_wl);
-  if (n_wl) launch(st, k_view_rows, n_wl, (const uint64_t *)sc.off, (const uint32_t *)sc.len, (const uint32_t *)wl_ids, n_wl, lv.off, lv.len);
-  HC(hipStreamSynchronize(st));
-  E->stats.subst_ms += now_ms() - Ts;
-  E->stats.nl_ms += now_ms() - Ts;
-
-  // ======================= rounds >= 2 (:613-646)
-  bool apply_round = apply_linear && no_rounds > 0 && n_wl > 0;
-  // streamed result: rows a later round touches are taken from the late region
-  uint8_t *so_dirty = nullptr;
-  if (so_early) {
-    so_dirty = A.get<uint8_t>("so.dirty", n_st ? n_st : 1);
-    if (n_st) HC(hipMemsetAsync(so_dirty, 0, n_st, st));
-  }
-  // A round's snapshot (single engine): the storage rows the round rewrote that stay storage rows go
-  // behind the early region right away -- final unless a later round rewrites them again (dirty once
-  // more: late at the end) -- so a round that rewrites most rows (the templated circuit's round 2)
-  // streams them while the run goes on instead of after it.  Skipped when the regions sized at the first
-  // snapshot cannot take them (the capacity hint grows for the next run).
-  auto snap_round = [&](const uint8_t *touched, const int32_t *turn, const DRows &pa, const DRows &pb, const DRows &pc) {
-    if (!so_dirty || !n_st || (E->comm && E->comm->world > 1)) return;
-    // the earlier snapshots' gathers read the early flags / offsets this one rewrites, and its own buffers
-    HC(hipStreamWaitEvent(st, E->ev_snap, 0));
-    U3 *elen = A.get<U3>("so.rlen", n_st), *eoff3 = A.get<U3>("so.roff", n_st);
-    const DRows *src[3] = {&pa, &pb, &pc};
-    const char *nm[3] = {"sor.a", "sor.b", "sor.c"};
-    DRows cp[3];  // copies of the selected rows' views (a later round re-points rows)
-    ViewCopy vc;
-    for (int q = 0; q < 3; ++q) {
-      cp[q] = *src[q];
-      cp[q].off = vc.off[q] = A.get<uint64_t>(std::string(nm[q]) + ".off", n_st);
-      cp[q].len = vc.len[q] = A.get<uint32_t>(std::string(nm[q]) + ".len", n_st);
-    }
-    launch(st, k_snap_lens_round, n_st, pa, pb, pc, touched, turn, (const uint32_t *)st_ids, (const uint8_t *)so_early, n_st, elen, vc);
-    const U3 et = excl_scan_u3(E, elen, eoff3, n_st, "sor");
-    const uint64_t e3[3] = {et.a, et.b, et.c};
-    if (!(e3[0] | e3[1] | e3[2])) return;
-    for (int q = 0; q < 3; ++q) E->snap_hint[q] = std::max(E->snap_hint[q], E->snap_e[q] + e3[q]);
-    for (int q = 0; q < 3; ++q)
-      if (E->snap_e[q] + e3[q] > E->snap_cap[q]) return;
-    launch(st, k_snap_mark_round, n_st, (const uint32_t *)st_ids, (const U3 *)elen, (const U3 *)eoff3,
-           U3{E->snap_e[0], E->snap_e[1], E->snap_e[2]}, n_st, so_early, so_eoff, so_dirty);
-    // the previous snapshot's gathers still read their view copies and elen / offsets (stc is in order)
-    HC(hipEventRecord(E->ev_snap0, st));
-    HC(hipStreamWaitEvent(E->stc, E->ev_snap0, 0));
-    for (int q = 0; q < 3; ++q) {
-      const uint64_t b = E->snap_e[q];
-      const std::string xn = std::string("out.") + "abc"[q];
-      uint32_t *col = A.get<uint32_t>(xn + ".xcol", 1);
-      uint64_t *val = A.get<uint64_t>(xn + ".xval", 1);
-      if (!e3[q]) continue;
-      E->kg[2].run(E->stc, 24 * n_st + 72 * e3[q], [&] {
-        launch(E->stc, k_snap_gather_st, n_st, E->F, cp[q], (const U3 *)elen, (const U3 *)eoff3, b, q, n_st, col, val);
-      });
-      HC(hipEventRecord(E->ev_snapq[3 + q], E->stc));
-      snap_push(E, {(uint32_t *)E->snap_host[2 * q] + b, col + b, 4 * e3[q], E->ev_snapq[3 + q]});
-      snap_push(E, {(uint64_t *)E->snap_host[2 * q + 1] + 4 * b, val + 4 * b, 32 * e3[q], E->ev_snapq[3 + q]});
-      E->snap_e[q] = b + e3[q];
-    }
-    HC(hipEventRecord(E->ev_snap, E->stc));
-    if (g_prof_env)
-      fprintf(stderr, "[rs-prof] stream: round snapshot %llu / %llu / %llu entries (%.1f MB)\n", (unsigned long long)e3[0],
-              (unsigned long long)e3[1], (unsigned long long)e3[2], 36e-6 * (e3[0] + e3[1] + e3[2]));
-  };
-  if (getenv("RS_DEBUG")) {
-    HC(hipStreamSynchronize(st));
-    fprintf(stderr, "[rs-debug] heap %p cap %llu top %llu n_st %llu n_wl %llu\n", (void *)heap_k,
-            (unsigned long long)E->heap_cap, (unsigned long long)heap_top, (unsigned long long)n_st, (unsigned long long)n_wl);
-    for (uint64_t r = 0; r < std::min<uint64_t>(n_st, 3); ++r) {
-      uint64_t o = 0; uint32_t l = 0;
-      HC(hipMemcpy(&o, tc_.off + r, 8, hipMemcpyDeviceToHost));
-      HC(hipMemcpy(&l, tc_.len + r, 4, hipMemcpyDeviceToHost));
-      std::vector<uint32_t> kk; std::vector<Fe> vv;
-      d2h_row(E, tc_, r, kk, vv);
-      fprintf(stderr, "[rs-debug]  st %llu C off %llu len %u:", (unsigned long long)r, (unsigned long long)o, l);
-      for (size_t i = 0; i < kk.size(); ++i) fprintf(stderr, " %u:%llu", kk[i], (unsigned long long)ffrom_mont(E->F, vv[i]).l[0]);
-      fprintf(stderr, "\n");
-    }
-  }
-  if (apply_round) {
-    // the non-linear signal map, kept on the host only for the signals a round substitutes:
-    // initial lists (round-1 storage rows, ascending ids; built on the GPU on demand) + appends
-    double Tm = now_ms();
-    DRows ia0 = ta_, ib0 = tb_, ic0 = tc_;  // snapshot of the round-1 storage rows
-    ia0.off = A.get<uint64_t>("m0.a.off", n_st); ia0.len = A.get<uint32_t>("m0.a.len", n_st);
-    ib0.off = A.get<uint64_t>("m0.b.off", n_st); ib0.len = A.get<uint32_t>("m0.b.len", n_st);
-    ic0.off = A.get<uint64_t>("m0.c.off", n_st); ic0.len = A.get<uint32_t>("m0.c.len", n_st);
-    if (n_st) {
-      HC(hipMemcpyAsync(ia0.off, ta_.off, 8 * n_st, hipMemcpyDeviceToDevice, st));
-      HC(hipMemcpyAsync(ia0.len, ta_.len, 4 * n_st, hipMemcpyDeviceToDevice, st));
-      HC(hipMemcpyAsync(ib0.off, tb_.off, 8 * n_st, hipMemcpyDeviceToDevice, st));
-      HC(hipMemcpyAsync(ib0.len, tb_.len, 4 * n_st, hipMemcpyDeviceToDevice, st));
-      HC(hipMemcpyAsync(ic0.off, tc_.off, 8 * n_st, hipMemcpyDeviceToDevice, st));
-      HC(hipMemcpyAsync(ic0.len, tc_.len, 4 * n_st, hipMemcpyDeviceToDevice, st));
-    }
-    // the appended lists of the non-linear signal map, lazily (maplists.hpp)
-    MapLists ML;
-    auto &minit = ML.minit;  // initial lists, queried signals only
-    uint8_t *qflag = A.get<uint8_t>("m.qflag", S);
-    HC(hipMemsetAsync(qflag, 0, S, st));
-    auto query_initial = [&](const std::vector<uint32_t> &sigs) {
-      std::vector<uint32_t> q;
-      for (uint32_t s : sigs)
-        if (!minit.count(s)) { minit[s]; q.push_back(s); }
-      if (q.empty() || n_st == 0) return;
-      uint32_t *d_q = A.get<uint32_t>("m.q", q.size());
-      h2d(E, d_q, q.data(), 4 * q.size());
-      launch(st, k_mark_list, q.size(), (const uint32_t *)d_q, (uint64_t)q.size(), qflag);
-      unsigned long long *d_cnt = A.get<unsigned long long>("m.cnt", 1);
-      uint64_t cap = std::max<uint64_t>(4 * q.size(), 1 << 16);
-      for (;;) {
-        uint64_t *d_pairs = A.get<uint64_t>("m.pairs", cap);
-        HC(hipMemsetAsync(d_cnt, 0, 8, st));
-        for (DRows *R : {&ia0, &ib0, &ic0}) { R->key = heap_k; R->val = heap_v; }
-        launch(st, k_emit_pairs, n_st, ia0, ib0, ic0, (const uint8_t *)qflag, d_pairs, d_cnt, cap);
-        unsigned long long cnt = 0;
-        HC(hipMemcpyAsync(&cnt, d_cnt, 8, hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-        if (cnt > cap) { cap = cnt; continue; }
-        std::vector<uint64_t> pairs(cnt);
-        if (cnt) {
-          HC(hipMemcpyAsync(pairs.data(), d_pairs, 8 * cnt, hipMemcpyDeviceToHost, st));
-          HC(hipStreamSynchronize(st));
-        }
-        std::sort(pairs.begin(), pairs.end());
-        for (uint64_t x : pairs) minit[(uint32_t)(x >> 32)].push_back((uint32_t)x);
-        break;
-      }
-      launch(st, k_unmark_list, q.size(), (const uint32_t *)d_q, (uint64_t)q.size(), qflag);
-    };
-    E->stats.subst_ms += now_ms() - Tm;
-    E->stats.map_ms += now_ms() - Tm;
-    int32_t *rank_of = A.get<int32_t>("rank_of", S);
-    HC(hipMemsetAsync(rank_of, 0xff, 4 * S, st));
-    int32_t *r_sub_of = A.get<int32_t>("r.sub_of", S);
-    HC(hipMemsetAsync(r_sub_of, 0xff, 4 * S, st));
-    while (apply_round) {
-      // linear_simplification over the current list
-      ElimOut er;
-      HC(hipMemsetAsync(r_sub_of, 0xff, 4 * S, st));
-      run_linear_simplification(E, lv, fl->use_old_heuristics, er, P, d_err, d_forb, r_sub_of, d_deleted, nullptr, nullptr,
-                                E->comm && E->comm->world > 1 && !E->log_on ? nlmap : nullptr);
-      if (E->log_on) log_linear_round(E, er, P);
-      E->stats.rounds++;
-      Marks MK;
-      MK.st = st;
-      MK.mark("start");
-      collect_leftovers(E, er, P, lc);
-      MK.mark("leftovers");
-      double Tr = now_ms();
-      // ordered substitutions of the round: cluster order, ascending `from` -- one sort of the
-      // (cluster, from) keys of the valid slots on the device; the host fetches the list only when
-      // a row turned linear or another round follows
-      const uint64_t n_slots = er.n_slots;
-      uint64_t nU = 0;
-      uint32_t *d_us = A.get<uint32_t>("r.us", 1), *d_U = A.get<uint32_t>("r.U", 1), *d_ulen = A.get<uint32_t>("r.ulen", 1);
-      uint64_t *d_uoff = A.get<uint64_t>("r.uoff", 1);
-      if (n_slots) {
-        uint64_t *vf = A.get<uint64_t>("r.vf", n_slots), *vp = A.get<uint64_t>("r.vp", n_slots);
-        launch(st, k_sub_valid, n_slots, (const uint32_t *)A.get<uint32_t>("cl.cid", 1), (const uint64_t *)A.get<uint64_t>("el.cl", 1),
-               (const uint32_t *)A.get<uint32_t>("el.n_sub", 1), n_slots, vf);
-        nU = excl_scan_u64(E, vf, vp, n_slots, "vf");
-        if (nU) {
-          uint64_t *uk = A.get<uint64_t>("r.uk", nU), *uk2 = A.get<uint64_t>("r.uk2", nU);
-          uint32_t *uv = A.get<uint32_t>("r.uv", nU);
-          d_U = A.get<uint32_t>("r.U", nU);
-          d_us = A.get<uint32_t>("r.us", nU);
-          d_uoff = A.get<uint64_t>("r.uoff", nU);
-          d_ulen = A.get<uint32_t>("r.ulen", nU);
-          launch(st, k_sub_keys, n_slots, (const uint32_t *)A.get<uint32_t>("cl.cid", 1), (const uint64_t *)vf,
-                 (const uint64_t *)vp, (const uint32_t *)A.get<uint32_t>("el.h_sig", 1), n_slots, uk, uv);
-          int cbits = 1;
-          while (cbits < 32 && (1ull << cbits) <= er.n_clusters) ++cbits;
-          sort_pairs(E, (const uint64_t *)uk, uk2, (const uint32_t *)uv, d_U, nU, 32 + cbits, "us");
-          launch(st, k_sub_info, nU, (const uint64_t *)uk2, (const uint32_t *)d_U, (const uint64_t *)A.get<uint64_t>("el.h_off", 1),
-                 (const uint32_t *)A.get<uint32_t>("el.h_len", 1), nU, d_us, d_uoff, d_ulen, rank_of);
-        }
-      }
-      std::vector<uint32_t> usig;  // host copy of the ordered `from` list, fetched on demand
-      auto need_usig = [&]() {
-        if (usig.size() == nU) return;
-        usig.resize(nU);
-        HC(hipMemcpyAsync(usig.data(), d_us, 4 * nU, hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-      };
-      MK.mark("order");
-      // apply to every storage row (apply_substitution_to_map, :345-396)
-      std::vector<std::pair<uint64_t, uint32_t>> turned;  // (order key, storage id)
-      if (n_st && nU) {
-        RoundArgs ra{};
-        ra.F = E->F;
-        ra.a = ta_; ra.b = tb_; ra.c = tc_;
-        uint64_t *ca = A.get<uint64_t>("r.capa", n_st), *cb = A.get<uint64_t>("r.capb", n_st), *cc = A.get<uint64_t>("r.capc", n_st);
-        ra.cap_a = ca; ra.cap_b = cb; ra.cap_c = cc;
-        ra.sub_of = r_sub_of;
-        ra.rank_of = rank_of;
-        ra.h_off = A.get<uint64_t>("el.h_off", 1);
-        ra.h_len = A.get<uint32_t>("el.h_len", 1);
-        ra.pk = P.pk;
-        ra.pv = P.pv;
-        ra.turn = A.get<int32_t>("r.turn", n_st);
-        ra.touched = A.get<uint8_t>("r.touched", n_st);
-        launch(st, k_round_count, n_st, ra);
-        U3 *cap3 = A.get<U3>("r.c3", n_st), *sc3 = A.get<U3>("r.s3", n_st);
-        launch(st, k_pack3, n_st, (const uint64_t *)ca, (const uint64_t *)cb, (const uint64_t *)cc, n_st, cap3);
-        const U3 q3 = excl_scan_u3(E, cap3, sc3, n_st, "r");
-        const uint64_t qt = q3.a + q3.b + q3.c;
-        heap_reserve(qt);
-        for (DRows *R : {&ta_, &tb_, &tc_, &lv}) { R->key = heap_k; R->val = heap_v; }
-        ra.a = ta_; ra.b = tb_; ra.c = tc_;
-        DRows oa = ta_, ob = tb_, oc = tc_;
-        oa.off = A.get<uint64_t>("r.oa.off", n_st); oa.len = A.get<uint32_t>("r.oa.len", n_st);
-        ob.off = A.get<uint64_t>("r.ob.off", n_st); ob.len = A.get<uint32_t>("r.ob.len", n_st);
-        oc.off = A.get<uint64_t>("r.oc.off", n_st); oc.len = A.get<uint32_t>("r.oc.len", n_st);
-        launch(st, k_set_offsets_u3, n_st, (const U3 *)sc3, heap_top, heap_top + q3.a, heap_top + q3.a + q3.b, n_st, oa.off,
-               ob.off, oc.off, (const U3 *)nullptr, (const uint32_t *)nullptr);
-        heap_top += qt;
-        ra.c_base = heap_top - q3.c;  // row scratch = 2 * (its C offset - c_base)
-        ra.oa = oa; ra.ob = ob; ra.oc = oc;
-        ra.tmpk = A.get<uint32_t>("r.tmpk", 2 * (q3.c + 1));
-        ra.tmpv = A.get<Fe>("r.tmpv", 2 * (q3.c + 1));
-        MK.mark("count");
-        {  // compact the touched rows: the fill's lanes all have work
-          uint64_t *tfl = A.get<uint64_t>("r.tfl", n_st), *tfp = A.get<uint64_t>("r.tfp", n_st);
-          uint32_t *tids = A.get<uint32_t>("r.touch_ids", n_st);
-          launch(st, k_touch_flags, n_st, (const uint64_t *)cc, n_st, tfl);
-          ra.n_ids = excl_scan_u64(E, tfl, tfp, n_st, "tfl");
-          if (ra.n_ids) launch(st, k_scatter_ids, n_st, (const uint64_t *)tfl, (const uint64_t *)tfp, n_st, tids);
-          ra.ids = tids;
-          HC(hipMemsetAsync(ra.turn, 0xff, 4 * n_st, st));
-          HC(hipMemsetAsync(ra.touched, 0, n_st, st));
-        }
-        ra.bytes = A.get<unsigned long long>("r.bytes", 1);
-        HC(hipMemsetAsync(ra.bytes, 0, 8, st));
-        if (ra.n_ids) {
-          FrameWaveArgs w{};
-          w.fr.F = E->F;
-          w.fr.sub_of = r_sub_of;
-          w.fr.h_off = ra.h_off; w.fr.h_len = ra.h_len; w.fr.pk = ra.pk; w.fr.pv = ra.pv;
-          w.in[0] = ta_; w.in[1] = tb_; w.in[2] = tc_;
-          w.out[0] = oa; w.out[1] = ob; w.out[2] = oc;
-          w.cap[0] = ca; w.cap[1] = cb; w.cap[2] = cc;
-          w.cap_by_row = 1;
-          w.ids = ra.ids;
-          w.n = ra.n_ids;
-          w.big = A.get<uint32_t>("r.big", ra.n_ids);
-          w.n_big = A.get<unsigned>("r.nbig", 2);
-          w.round = 1;
-          w.touched = ra.touched;
-          w.turn_list = A.get<uint32_t>("r.turnlist", ra.n_ids);
-          w.n_turn = w.n_big + 1;
-          w.err = d_fw_err;
-          w.bytes = ra.bytes;
-          HC(hipMemsetAsync(w.n_big, 0, 8, st));
-#ifdef RS_FWCLK
-          w.clk = A.get<unsigned long long>("fw.clkr", 32);
-          HC(hipMemsetAsync(w.clk, 0, 8 * 32, st));
-#endif
-          RoundArgs rb = ra, rt = ra;
-          rb.rlist = w.big; rb.n_rlist = w.n_big;
-          rt.rlist = w.turn_list; rt.n_rlist = w.n_turn;
-          HC(hipEventRecord(E->ev0, st));
-          launch_capped(st, k_frames_wave<1>, ra.n_ids, kFwBlocks, w);
-          {  // the rows too long for a wave's LDS batch: A / B / C expanded by one device-wide sort
-            unsigned nbig = 0;
-            HC(hipMemcpyAsync(&nbig, w.n_big, 4, hipMemcpyDeviceToHost, st));
-            HC(hipStreamSynchronize(st));
-#ifdef RS_FWCLK
-            if (g_prof_env) {
-              unsigned long long c[32];
-              HC(hipMemcpy(c, w.clk, sizeof c, hipMemcpyDeviceToHost));
-              fprintf(stderr, "[rs-prof] round frames clocks (Mcycles summed over waves): groups %.1f entries %.1f terms %.1f "
-                      "rank %.1f emit %.1f rows %.1f plan %.1f | batches %llu, wave total %.1f over %llu waves | emit: loads %.1f "
-                      "values %.1f sync %.1f stores %.1f | %u rows over a batch of %llu\n", c[0] / 1e6, c[1] / 1e6, c[2] / 1e6,
-                      c[3] / 1e6, c[5] / 1e6, c[6] / 1e6, c[7] / 1e6, c[8], c[9] / 1e6, c[10], c[16] / 1e6, c[17] / 1e6,
-                      c[18] / 1e6, c[19] / 1e6, nbig, (unsigned long long)ra.n_ids);
-            }
-#endif
-            if (nbig) {
-              const uint64_t nseg = 3ull * nbig;
-              uint64_t *xc = A.get<uint64_t>("x.cnt", nseg), *xo = A.get<uint64_t>("x.off", nseg + 1);
-              launch(st, k_xrow_count, nseg, rb, nseg, xc);
-              const uint64_t T = excl_scan_u64(E, xc, xo, nseg, "xrow");
-              h2d(E, xo + nseg, &T, 8);
-              if (T) {
-                uint64_t *xk = A.get<uint64_t>("x.k", T), *xk2 = A.get<uint64_t>("x.k2", T);
-                uint32_t *xi = A.get<uint32_t>("x.i", T), *xi2 = A.get<uint32_t>("x.i2", T);
-                Fe *xv = A.get<Fe>("x.v", T);
-                launch(st, k_xrow_expand, 64 * nseg, rb, nseg, (const uint64_t *)xo, xk, xv, xi);
-                int sb = 1;
-                while (sb < 32 && (1ull << sb) <= nseg) ++sb;
-                sort_pairs(E, (const uint64_t *)xk, xk2, (const uint32_t *)xi, xi2, T, 32 + sb, "xrow");
-                launch(st, k_xrow_combine, 64 * nseg, rb, nseg, (const uint64_t *)xo, (const uint64_t *)xk2,
-                       (const uint32_t *)xi2, (const Fe *)xv);
-              } else {
-                launch(st, k_xrow_combine, 64 * nseg, rb, nseg, (const uint64_t *)xo, (const uint64_t *)nullptr,
-                       (const uint32_t *)nullptr, (const Fe *)nullptr);
-              }
-              rb.pre_expanded = 1;
-            }
-          }
-          launch(st, k_round_fill, ra.n_ids, rb);
-          launch(st, k_round_turn, ra.n_ids, rt);
-          HC(hipEventRecord(E->ev1, st));
-          if (g_prof_env) {
-            unsigned nb[2] = {0, 0};
-            HC(hipMemcpyAsync(nb, w.n_big, 8, hipMemcpyDeviceToHost, st));
-            HC(hipStreamSynchronize(st));
-            fprintf(stderr, "[rs-prof] round: %llu rows, %u over a wave batch, %u turn\n", (unsigned long long)ra.n_ids, nb[0], nb[1]);
-          }
-          float fm = 0;
-          unsigned long long fb = 0;
-          HC(hipMemcpyAsync(&fb, ra.bytes, 8, hipMemcpyDeviceToHost, st));
-          HC(hipEventSynchronize(E->ev1));
-          HC(hipStreamSynchronize(st));
-          HC(hipEventElapsedTime(&fm, E->ev0, E->ev1));
-          E->stats.round_fill_ms += fm;
-          E->stats.round_fill_bytes += fb;
-          E->stats.round_fill_launches++;
-        }
-        MK.mark("fill");
-        if (getenv("RS_DEBUG")) debug_check_round(E, ra, n_st, qt);
-        launch(st, k_commit_round, n_st, (const uint8_t *)ra.touched, (const int32_t *)ra.turn, n_st, ta_, tb_, tc_, oa, ob, oc);
-        if (so_dirty) launch(st, k_or_u8, n_st, (const uint8_t *)ra.touched, n_st, so_dirty);
-        snap_round(ra.touched, ra.turn, ta_, tb_, tc_);
-        // turned rows
-        uint64_t *tf = A.get<uint64_t>("r.tf", n_st), *tp = A.get<uint64_t>("r.tp", n_st);
-        launch(st, k_turn_flags, n_st, (const int32_t *)ra.turn, n_st, tf);
-        uint64_t n_turn = excl_scan_u64(E, tf, tp, n_st, "tf");
-        uint32_t *tids = A.get<uint32_t>("r.tids", n_turn);
-        launch(st, k_scatter_ids, n_st, (const uint64_t *)tf, (const uint64_t *)tp, n_st, tids);
-        std::vector<uint32_t> htids(n_turn);
-        std::vector<int32_t> hturn(n_turn);  // turn value of each turned row (aligned with htids)
-        if (n_turn) {
-          int32_t *d_tt = A.get<int32_t>("r.tturn", n_turn);
-          launch(st, k_gather_u32, n_turn, (const uint32_t *)ra.turn, (const uint32_t *)tids, (uint32_t *)d_tt, n_turn);
-          HC(hipMemcpyAsync(htids.data(), tids, 4 * n_turn, hipMemcpyDeviceToHost, st));
-          HC(hipMemcpyAsync(hturn.data(), d_tt, 4 * n_turn, hipMemcpyDeviceToHost, st));
-          HC(hipStreamSynchronize(st));
-          need_usig();
-        }
-        std::unordered_map<uint32_t, std::vector<uint32_t>> ext;  // appended lists of those signals
-        {  // initial map lists of the turning substitutions' signals only
-          double Tq = now_ms();
-          std::vector<uint32_t> qs;
-          for (uint64_t i = 0; i < n_turn; ++i) qs.push_back(usig[hturn[i]]);
-          std::sort(qs.begin(), qs.end());
-          qs.erase(std::unique(qs.begin(), qs.end()), qs.end());
-          query_initial(qs);
-          ext = ML.resolve(qs, query_initial);
-          E->stats.map_ms += now_ms() - Tq;
-        }
-        // order key: (rank of the turning substitution, first position in map[from])
-        for (uint64_t ti = 0; ti < n_turn; ++ti) {
-          const uint32_t r = htids[ti];
-          int32_t q = hturn[ti];
-          uint32_t from = usig[q];
-          uint64_t pos = UINT64_MAX;
-          const std::vector<uint32_t> &L0 = minit[from];
-          auto lb = std::lower_bound(L0.begin(), L0.end(), r);  // initial lists are ascending
-          if (lb != L0.end() && *lb == r) pos = lb - L0.begin();
-          if (pos == UINT64_MAX) {
-            auto it = ext.find(from);
-            if (it != ext.end())
-              for (uint64_t t = 0; t < it->second.size(); ++t)
-                if (it->second[t] == r) { pos = L0.size() + t; break; }
-          }
-          if (pos == UINT64_MAX) throw RsError(RS_E_INTERNAL, "substituted row missing from the signal map");
-          turned.push_back({((uint64_t)q << 32) | (pos & 0xffffffffu), r});
-        }
-        std::sort(turned.begin(), turned.end());
-        MK.mark("turned");
-        if (getenv("RS_DEBUG")) {
-          std::vector<uint8_t> tch(n_st);
-          HC(hipMemcpy(tch.data(), ra.touched, n_st, hipMemcpyDeviceToHost));
-          uint64_t nt = 0;
-          for (auto x : tch) nt += x;
-          fprintf(stderr, "[rs-debug] round: nU=%llu touched=%llu turned=%llu:", (unsigned long long)nU,
-                  (unsigned long long)nt, (unsigned long long)n_turn);
-          for (auto &t : turned) fprintf(stderr, " %u(q%llu)", t.second, (unsigned long long)(t.first >> 32));
-          fprintf(stderr, "\n");
-        }
-      }
-      MK.mark("appends");
-      if (nU) launch(st, k_unset_rank, nU, (const uint32_t *)d_us, nU, rank_of);  // reset the dense rank index
-      // next linear list: the turned rows, non-empty, in linear_id order
-      std::vector<uint32_t> next_ids;
-      {
-        if (!turned.empty()) {  // C lengths of the turned rows only
-          std::vector<uint32_t> tid_(turned.size()), tlen(turned.size());
-          for (size_t i = 0; i < turned.size(); ++i) tid_[i] = turned[i].second;
-          uint32_t *d_t = A.get<uint32_t>("r.tid", tid_.size()), *d_tl = A.get<uint32_t>("r.tlen", tid_.size());
-          h2d(E, d_t, tid_.data(), 4 * tid_.size());
-          launch(st, k_gather_u32, tid_.size(), (const uint32_t *)tc_.len, (const uint32_t *)d_t, d_tl, (uint64_t)tid_.size());
-          HC(hipMemcpyAsync(tlen.data(), d_tl, 4 * tlen.size(), hipMemcpyDeviceToHost, st));
-          HC(hipStreamSynchronize(st));
-          for (size_t i = 0; i < turned.size(); ++i)
-            if (tlen[i]) next_ids.push_back(turned[i].second);
-        }
-      }
-      uint64_t nn = next_ids.size();
-      // map appends (:369-377): the key set on the device; the row lists (positions for a later
-      // round's ordering) only when another round follows
-      if (nU) {
-        launch(st, k_append_marks, nU, (const uint32_t *)d_us, (const uint64_t *)d_uoff, (const uint32_t *)d_ulen, nU,
-               (const uint32_t *)P.pk, nlmap);
-      }
-      const bool another = nn > 0 && (no_rounds > 0 ? no_rounds - 1 : 0) > 0;
-      if (another) {
-        double Tq = now_ms();
-        need_usig();
-        // this round's batch of appends: every substitution's `from` and RHS keys (no values).  The
-        // keys are copied on the device now (the next round's elimination reuses the pool) and come to
-        // the host only if a later round resolves a list through this batch -- most never do (the
-        // templated circuit's round 2: 9.8 ms of D2H and host copies saved per call)
-        MapLists::Batch B;
-        B.from = usig;
-        const size_t bi = ML.batches.size();
-        const std::string bn = "ml." + std::to_string(bi);
-        uint64_t *d_optr = A.get<uint64_t>(bn + ".ptr", nU + 1);
-        uint64_t *d_len64 = A.get<uint64_t>(bn + ".len", nU + 1);
-        launch(st, k_u32_to_u64, nU, (const uint32_t *)d_ulen, d_len64, nU);
-        HC(hipMemsetAsync(d_len64 + nU, 0, 8, st));
-        const uint64_t tot = excl_scan_u64(E, d_len64, d_optr, nU + 1, "mlb");
-        uint32_t *d_keys = A.get<uint32_t>(bn + ".keys", std::max<uint64_t>(tot, 1));
-        if (tot)
-          launch(st, k_pool_keys, 64 * nU, (const uint64_t *)d_uoff, (const uint32_t *)d_ulen, (const uint64_t *)d_optr, nU,
-                 (const uint32_t *)P.pk, d_keys);
-        B.load = [E, d_optr, d_keys, nU, tot](MapLists::Batch &Bt) {
-          Bt.ptr.resize(nU + 1);
-          Bt.keys.resize(tot);
-          HC(hipMemcpyAsync(Bt.ptr.data(), d_optr, 8 * (nU + 1), hipMemcpyDeviceToHost, E->st));
-          if (tot) HC(hipMemcpyAsync(Bt.keys.data(), d_keys, 4 * tot, hipMemcpyDeviceToHost, E->st));
-          HC(hipStreamSynchronize(E->st));
-        };
-        ML.add_batch(std::move(B));
-        E->stats.map_ms += now_ms() - Tq;
-      }
-      MK.mark("appends2");
-      lv.n = nn;
-      lv.off = A.get<uint64_t>("lv.off", nn);
-      lv.len = A.get<uint32_t>("lv.len", nn);
-      lv.key = heap_k;
-      lv.val = heap_v;
-      if (nn) {
-        uint32_t *d_ids = A.get<uint32_t>("lv.ids", nn);
-        h2d(E, d_ids, next_ids.data(), 4 * nn);
-        launch(st, k_view_rows, nn, (const uint64_t *)tc_.off, (const uint32_t *)tc_.len, (const uint32_t *)d_ids, nn, lv.off, lv.len);
-      }
-      // emptied storage rows (storage.replace(c_id, C::empty()))
-      if (!turned.empty()) {
-        std::vector<uint32_t> all;
-        for (auto &t : turned) all.push_back(t.second);
-        uint32_t *d_all = A.get<uint32_t>("r.all", all.size());
-        h2d(E, d_all, all.data(), 4 * all.size());
-        launch(st, k_zero_c, all.size(), (const uint32_t *)d_all, (uint64_t)all.size(), tc_.len);
-      }
-      HC(hipStreamSynchronize(st));
-      if (getenv("RS_DEBUG")) {
-        for (uint64_t r = 0; r < std::min<uint64_t>(n_st, 24); ++r) {
-          uint32_t la = 0, lb = 0, lc = 0;
-          HC(hipMemcpy(&la, ta_.len + r, 4, hipMemcpyDeviceToHost));
-          HC(hipMemcpy(&lb, tb_.len + r, 4, hipMemcpyDeviceToHost));
-          HC(hipMemcpy(&lc, tc_.len + r, 4, hipMemcpyDeviceToHost));
-          std::vector<uint32_t> kk;
-          std::vector<Fe> vv;
-          d2h_row(E, tc_, r, kk, vv);
-          fprintf(stderr, "[rs-debug] storage %llu lens %u %u %u C:", (unsigned long long)r, la, lb, lc);
-          for (size_t i = 0; i < kk.size(); ++i) fprintf(stderr, " %u:%llu", kk[i], (unsigned long long)ffrom_mont(E->F, vv[i]).l[0]);
-          fprintf(stderr, "\n");
-        }
-      }
-      MK.mark("next");
-      MK.dump();
-      if (g_prof_env) fprintf(stderr, "[rs-prof] round: nU %llu n_st %llu next %llu\n", (unsigned long long)nU, (unsigned long long)n_st, (unsigned long long)nn);
-      E->stats.subst_ms += now_ms() - Tr;
-      E->stats.rounds_ms += now_ms() - Tr;
-      if (no_rounds > 0) no_rounds--;
-      apply_round = nn > 0 && no_rounds > 0;
-    }
-  }
-  // ======================= final assembly (:648-729)
-  double Tf = now_ms();
-  // leftover linear rows (rounds exhausted) and lconst: appended after the storage rows; their
-  // signals join the non-linear map (:648-686)
-  const DRows lcv = lc.view(A);
-  if (lv.n) launch(st, k_mark_keys, lv.n, lv, nlmap);
-  if (lcv.n) launch(st, k_mark_keys, lcv.n, lcv, nlmap);
-  HC(hipMemsetAsync(nlmap, 0, 1, st));  // the constant key is not a signal
-  uint32_t *kept = A.get<uint32_t>("fin.kept", S);
-  uint64_t *kept64 = A.get<uint64_t>("fin.kept64", S);
-  uint64_t *rank = A.get<uint64_t>("fin.rank", S);
-  int32_t *l2w = A.get<int32_t>("fin.l2w", S);
-  launch(st, k_kept, S, (const uint8_t *)d_deleted, (const uint8_t *)d_forb, (const uint8_t *)nlmap, kept, S);
-  launch(st, k_u32_to_u64, S, (const uint32_t *)kept, kept64, S);
-  E->n_wires = excl_scan_u64(E, kept64, rank, S, "kept");
-  launch(st, k_l2w, S, (const uint32_t *)kept, (const uint64_t *)rank, l2w, S);
-  {
-    uint64_t lo = E->n_pub_out + 1, hi = E->n_pub_out + E->n_pub_in + E->n_priv_in;
-    uint64_t del_in = 0;
-    if (hi >= lo && lo < S) {
-      uint64_t cnt = std::min<uint64_t>(hi, S - 1) - lo + 1;
-      std::vector<uint32_t> k(cnt);
-      HC(hipMemcpyAsync(k.data(), kept + lo, 4 * cnt, hipMemcpyDeviceToHost, st));
-      HC(hipStreamSynchronize(st));
-      for (uint32_t x : k) del_in += x ? 0 : 1;
-    }
-    E->npiw = E->n_priv_in - del_in;
-  }
-  // output rows: storage (non-empty) ++ leftover linear ++ lconst, empty rows dropped
-  // (extract_with(is_empty), :697); the last two are C-only ("extras")
-  {
-    uint64_t *nef = A.get<uint64_t>("fin.nef", n_st), *nep = A.get<uint64_t>("fin.nep", n_st);
-    uint64_t n_keep = 0;
-    if (n_st) {
-      launch(st, k_nonempty_flags, n_st, (const uint32_t *)ta_.len, (const uint32_t *)tb_.len, (const uint32_t *)tc_.len, n_st, nef);
-      n_keep = excl_scan_u64(E, nef, nep, n_st, "ne");
-    }
-    uint32_t *keep_ids = A.get<uint32_t>("fin.keep", n_keep);
-    if (n_keep) launch(st, k_scatter_ids, n_st, (const uint64_t *)nef, (const uint64_t *)nep, n_st, keep_ids);
-    const DRows xsrc[2] = {lv, lcv};
-    const uint64_t zn = std::max<uint64_t>(lv.n, lcv.n);
-    uint32_t *zero_len = A.get<uint32_t>("fin.zlen", zn);
-    if (zn) HC(hipMemsetAsync(zero_len, 0, 4 * zn, st));
-    uint32_t *x_ids[2];
-    uint64_t n_x[2] = {0, 0}, x_at[2];
-    for (int x = 0; x < 2; ++x) {
-      const DRows &V = xsrc[x];
-      x_ids[x] = A.get<uint32_t>(x ? "fin.lcids" : "fin.lvids", V.n);
-      if (!V.n) continue;
-      uint64_t *lf = A.get<uint64_t>("fin.xf", V.n), *lp = A.get<uint64_t>("fin.xp", V.n);
-      launch(st, k_nonempty_flags, V.n, (const uint32_t *)zero_len, (const uint32_t *)zero_len, (const uint32_t *)V.len, V.n, lf);
-      n_x[x] = excl_scan_u64(E, lf, lp, V.n, "xf");
-      launch(st, k_scatter_ids, V.n, (const uint64_t *)lf, (const uint64_t *)lp, V.n, x_ids[x]);
-    }
-    x_at[0] = n_keep;
-    x_at[1] = n_keep + n_x[0];
-    const uint64_t n_out = n_keep + n_x[0] + n_x[1];
-    if (n_keep > n_st || n_x[0] > lv.n || n_x[1] > lcv.n) throw RsError(RS_E_INTERNAL, "final assembly: row counts out of range");
-    E->out_n_dev = n_out;
-    const DRows *parts[3] = {&ta_, &tb_, &tc_};
-    const char *nm[3] = {"out.a", "out.b", "out.c"};
-    // the streamed layout covers this engine's rows: all of them, or sharded its share -- the kept
-    // storage rows of its non-linear rows (a run [k_lo, k_hi) of the keep list), the last rank also
-    // the two C-only tails
-    Comm *CMf = E->comm.get();
-    const bool shard = E->snap_on && CMf && CMf->world > 1;
-    uint64_t k_lo = 0, k_hi = n_keep;
-    bool with_x = true;
-    if (shard) {
-      uint64_t kr[2] = {0, 0};
-      if (n_keep) {
-        uint64_t *d_kr = A.get<uint64_t>("fin.krange", 2);
-        launch(st, k_keep_range, 2, (const uint32_t *)keep_ids, n_keep, (const uint32_t *)st_ids, E->nl_lo, E->nl_hi, d_kr);
-        HC(hipMemcpyAsync(kr, d_kr, 16, hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-      }
-      k_lo = kr[0];
-      k_hi = std::max(kr[0], kr[1]);
-      with_x = CMf->rank == CMf->world - 1;
-    }
-    E->sh_klo = k_lo;
-    E->sh_khi = k_hi;
-    const uint64_t own = k_hi - k_lo;
-    const uint32_t *own_ids = keep_ids + k_lo;
-    const uint64_t xl_at[2] = {own, own + (with_x ? n_x[0] : 0)};
-    const uint64_t xl_n[2] = {with_x ? n_x[0] : 0, with_x ? n_x[1] : 0};
-    const uint64_t m_loc = own + xl_n[0] + xl_n[1];
-    for (int q = 0; q < 3; ++q) {
-      uint64_t *lens = A.get<uint64_t>(std::string(nm[q]) + ".lens", n_out + 1);
-      uint64_t *ptr = A.get<uint64_t>(std::string(nm[q]) + ".ptr", n_out + 1);
-      if (n_keep) launch(st, k_row_lens, n_keep, *parts[q], (const uint32_t *)keep_ids, n_keep, lens);
-      DRows xq[2];
-      for (int x = 0; x < 2; ++x) {
-        xq[x] = xsrc[x];
-        if (q < 2) xq[x].len = zero_len;
-        if (n_x[x]) launch(st, k_row_lens, n_x[x], xq[x], (const uint32_t *)x_ids[x], n_x[x], lens + x_at[x]);
-        E->fin_xq[x][q] = xq[x];
-      }
-      HC(hipMemsetAsync(lens + n_out, 0, 8, st));
-      uint64_t tot = excl_scan_u64(E, lens, ptr, n_out + 1, nm[q]);
-      E->out_nnz[q] = tot;
-      E->fin_parts[q] = *parts[q];
-      if (!E->snap_on) continue;
-      // streamed layout: the rows not reused from the early region, after it
-      uint64_t *late = A.get<uint64_t>(std::string(nm[q]) + ".late", m_loc + 1);
-      uint64_t *lptr = A.get<uint64_t>(std::string(nm[q]) + ".lptr", m_loc + 1);
-      if (own) launch(st, k_out_late_lens, own, *parts[q], own_ids, own, (const uint32_t *)st_ids, (const uint8_t *)so_early,
-                      (const uint8_t *)so_dirty, late);
-      if (xl_n[0]) launch(st, k_row_lens, xl_n[0], xq[0], (const uint32_t *)x_ids[0], xl_n[0], late + xl_at[0]);
-      if (xl_n[1]) launch(st, k_lc_late_lens, xl_n[1], xq[1], (const uint32_t *)x_ids[1], xl_n[1], E->lc_snap_n, late + xl_at[1]);
-      HC(hipMemsetAsync(late + m_loc, 0, 8, st));
-      const uint64_t L = excl_scan_u64(E, late, lptr, m_loc + 1, "late");
-      const uint64_t base = E->snap_e[q], ext = base + L;
-      E->out_ext[q] = ext;
-      uint64_t *beg = A.get<uint64_t>(std::string(nm[q]) + ".beg", m_loc + 1);
-      uint64_t *end = A.get<uint64_t>(std::string(nm[q]) + ".end", m_loc + 1);
-
-      if (own) launch(st, k_out_extent, own, *parts[q], own_ids, own, (const uint32_t *)st_ids, (const uint8_t *)so_early,
-                      (const uint8_t *)so_dirty, (const U3 *)so_eoff, q, base, (const uint64_t *)lptr, beg, end);
-      if (xl_n[0])
-        launch(st, k_out_extent, xl_n[0], xq[0], (const uint32_t *)x_ids[0], xl_n[0], (const uint32_t *)nullptr, (const uint8_t *)nullptr,
-               (const uint8_t *)nullptr, (const U3 *)nullptr, q, base, (const uint64_t *)(lptr + xl_at[0]), beg + xl_at[0], end + xl_at[0]);
-      if (xl_n[1])
-        launch(st, k_lc_extent, xl_n[1], xq[1], (const uint32_t *)x_ids[1], xl_n[1], E->lc_snap_n, E->lc_snap_base, q, base,
-               (const uint64_t *)(lptr + xl_at[1]), beg + xl_at[1], end + xl_at[1]);
-      launch(st, k_set_u64, 1, beg + m_loc, ext);
-      {  // ABI 8: per row its length (+ RS_ROW_JUMP) and the jump table -- what crosses the link
-        uint32_t *len32 = A.get<uint32_t>(std::string(nm[q]) + ".len32", m_loc + 1);
-        uint64_t *jf = A.get<uint64_t>(std::string(nm[q]) + ".jf", m_loc + 1);
-        uint64_t *jpos = A.get<uint64_t>(std::string(nm[q]) + ".jpos", m_loc + 1);
-        uint64_t nj = 0;
-        if (m_loc) {
-          launch(st, k_out_jumps, m_loc, (const uint64_t *)beg, (const uint64_t *)end, m_loc, shard ? 1 : 0, len32, jf);
-          nj = excl_scan_u64(E, jf, jpos, m_loc, "jump");
-        }
-        uint64_t *jtab = A.get<uint64_t>(std::string(nm[q]) + ".jtab", nj + 1);
-        if (nj) launch(st, k_out_jtab, m_loc, (const uint64_t *)beg, (const uint64_t *)jf, (const uint64_t *)jpos, m_loc, (uint64_t)0, jtab);
-        E->out_njump[q] = nj;
-        if (shard) (void)A.get<uint64_t>(std::string(nm[q]) + ".jtabx", nj + 1);  // fetch_result_shared's rebased copy
-      }
-      // the device copy of the whole layout grows past the early region when it must (the
-      // early region is copied along once its gather is done)
-      const std::string xc = std::string(nm[q]) + ".xcol", xv = std::string(nm[q]) + ".xval";
-      if (A.cap_bytes(xc) < 4 * ext || A.cap_bytes(xv) < 32 * ext) snap_join(E);  // its D2H reads them
-      A.grow_keep<uint32_t>(xc, ext, base, E->stc, st);
-      A.grow_keep<uint64_t>(xv, 4 * ext, 4 * base, E->stc, st);
-      uint32_t *col = A.get<uint32_t>(xc, ext);
-      uint64_t *val = A.get<uint64_t>(xv, 4 * ext);
-      E->kg[2].run(st, 30 * (own + xl_n[0] + xl_n[1]) + 72 * L, [&] {
-        if (own) launch(st, k_gather_late, own, E->F, *parts[q], own_ids, own, (const uint32_t *)st_ids, (const uint8_t *)so_early,
-                        (const uint8_t *)so_dirty, (const uint64_t *)lptr, col + base, val + 4 * base);
-        if (xl_n[0])
-          launch(st, k_gather_late, xl_n[0], E->F, xq[0], (const uint32_t *)x_ids[0], xl_n[0], (const uint32_t *)nullptr,
-                 (const uint8_t *)nullptr, (const uint8_t *)nullptr, (const uint64_t *)(lptr + xl_at[0]), col + base, val + 4 * base);
-        if (xl_n[1])
-          launch(st, k_lc_gather_late, xl_n[1], E->F, xq[1], (const uint32_t *)x_ids[1], xl_n[1], E->lc_snap_n,
-                 (const uint64_t *)(lptr + xl_at[1]), col + base, val + 4 * base);
-      });
-    }
-    if (shard) {  // a share past its capacity: the region regrows and every rank copies its whole layout
-      uint64_t over = 0;
-      for (int q = 0; q < 3; ++q) over |= E->out_ext[q] > E->sh_cap[q];
-      if (CMf->max_u64(over, st)) {
-        snap_join(E);  // the early copies into the old region are done (they are redone below)
-        for (int q = 0; q < 3; ++q) E->sh_cap[q] = CMf->max_u64(E->out_ext[q] + E->out_ext[q] / 4 + 65536, st);
-        E->sh_ent = CMf->shared_host(0, sh_ent_bytes(E), st);
-        // (the first snapshot's shared_host already fell back when the host had no room; a regrow
-        // that fails here is an error every rank reports alike)
-        if (!E->sh_ent) throw RsError(RS_E_RCCL, "no shared host memory for the sharded result");
-        E->sh_full = true;
-      }
-    }
-    E->fin_keep = n_keep;
-    E->fin_keep_ids = keep_ids;
-    for (int x = 0; x < 2; ++x) {
-      E->fin_xn[x] = n_x[x];
-      E->fin_x_ids[x] = x_ids[x];
-    }
-    E->fin_gen = A.gen;
-    if (!E->snap_on) ensure_csr(E);
-  }
-  load_wait_all(E);  // a group the path never needed (e.g. no non-linear rows) is still checked
-  int err = 0, fw_err = 0;
-  HC(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
-  HC(hipMemcpyAsync(&fw_err, d_fw_err, 4, hipMemcpyDeviceToHost, st));
-  HC(hipStreamSynchronize(st));
-  if (err) throw RsError(RS_E_INVALID, "input rejected by the device checks (code " + std::to_string(err) + ")");
-  if (fw_err) throw RsError(RS_E_INTERNAL, "frames batch over its bounds (code " + std::to_string(fw_err) + ")");
-  E->stats.final_ms = now_ms() - Tf;
-  E->stats.total_ms = now_ms() - T0;
-  if (g_prof_env) {
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess)
-      fprintf(stderr, "[rs-prof] device memory in use after the run: %.1f of %.1f GB (heap %.1f GB)\n", (tot - fr) / 1e9, tot / 1e9,
-              36e-9 * E->heap_cap);
-    std::vector<std::pair<size_t, std::string>> big;
-    size_t sum = 0;
-    for (auto &kv : A.bufs) {
-      big.push_back({kv.second.cap, kv.first});
-      sum += kv.second.cap;
-    }
-    std::sort(big.rbegin(), big.rend());
-    fprintf(stderr, "[rs-prof] arena %.1f GB in %zu buffers; largest:", sum / 1e9, big.size());
-    for (size_t i = 0; i < big.size() && i < 16; ++i) fprintf(stderr, " %s %.2f", big[i].second.c_str(), big[i].first / 1e9);
-    fprintf(stderr, "\n");
-  }
-  E->stats.h2d_wait_ms = E->h2d_wait_ms;
-  E->kg[0].collect(E->stats.check_ms, E->stats.check_bytes, E->stats.check_launches);
-  E->kg[1].collect(E->stats.ragged_ms, E->stats.ragged_bytes, E->stats.ragged_launches);
-  E->kg[2].collect(E->stats.gather_ms, E->stats.gather_bytes, E->stats.gather_launches);
-  {  // B_alg: the in-kernel counters + input / output entries and rows + the label map
-    const uint64_t z_in = E->ce.nnz + E->eq.nnz + E->lin.nnz + E->na.nnz + E->nb.nnz + E->nc.nnz;
-    const uint64_t r_in = E->ce.n + E->eq.n + E->lin.n + E->na.n;
-    const uint64_t z_out = E->out_nnz[0] + E->out_nnz[1] + E->out_nnz[2], r_out = E->out_n_dev;
-    const rs_stats &s = E->stats;
-    E->stats.alg_bytes = s.elim_bytes + s.big_main_bytes + s.big_finish_bytes + s.apply_bytes + s.round_fill_bytes +
-                         s.cluster_bytes + 36 * (z_in + z_out) + 8 * (r_in + r_out) + 8 * S;
-  }
-  E->have_result = true;
-}
+#include "run.hpp"
 
 }  // namespace rs
 
@@ -4142,7 +2633,7 @@ namespace rs {
 // narrowed by an earlier one.  near_gpu_cpus: that node's CPU set among the creator's allowed CPUs
 // (the count; 0: no binding, e.g. RS_NO_CPU_BIND=1, one node, or no sysfs entry).
 static int near_gpu_cpus(int device, cpu_set_t *want_out) {
-  if (getenv("RS_NO_CPU_BIND")) return 0;
+  if (env_flag("RS_NO_CPU_BIND")) return 0;
   char bus[64] = {0};
   if (hipDeviceGetPCIBusId(bus, sizeof bus, device) != hipSuccess) return 0;
   for (char *c = bus; *c; ++c) *c = (char)tolower(*c);
@@ -4223,7 +2714,7 @@ int rs_engine_create(int device, rs_engine **eng) {
     // copies -- is made with the full mask and shares its queue with nothing (RS_POOLED_STREAMS=1: a
     // pooled one; RS_CUMASK_STREAMS=1: every normal-priority stream dedicated, measured no better).
     // A CU-mask stream blocks with the null stream: nothing in a run uses it (E->srd takes host reads).
-    const bool pooled = getenv("RS_POOLED_STREAMS") != nullptr, all_masked = getenv("RS_CUMASK_STREAMS") != nullptr;
+    const bool pooled = env_flag("RS_POOLED_STREAMS"), all_masked = env_flag("RS_CUMASK_STREAMS");
     std::vector<uint32_t> cu_mask((E->n_cu + 31) / 32, 0u);
     for (uint32_t c = 0; c < E->n_cu; ++c) cu_mask[c / 32] |= 1u << (c % 32);
     auto mk_stream = [&](hipStream_t *sp, bool dedicated) {
@@ -4244,33 +2735,24 @@ int rs_engine_create(int device, rs_engine **eng) {
     {  // the small clusters and the tail's second group: least priority, so the tail's first group (the
        // first frames pass's critical path) finds CUs before their wide finish does
       int lo = 0, hi = 0;
-      if (getenv("RS_STE_DEFAULT") || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess ||
+      if (env_flag("RS_STE_DEFAULT") || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess ||
           hipStreamCreateWithPriority(&E->ste, hipStreamNonBlocking, lo) != hipSuccess)
         HC(hipStreamCreateWithFlags(&E->ste, hipStreamNonBlocking));
       if (g_prof_env) fprintf(stderr, "[rs-prof] stream priorities: least %d greatest %d\n", lo, hi);
     }
     mk_stream(&E->stg, all_masked);
-    for (auto &ev : E->evg) HC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HC(hipEventCreateWithFlags(&E->ev_gjoin, hipEventDisableTiming));
     for (auto &g : E->evt)
       for (auto &ev : g) HC(hipEventCreate(&ev));
     for (auto &ev : E->evc) HC(hipEventCreate(&ev));
     for (auto &ev : E->evgt) HC(hipEventCreate(&ev));
     for (auto &ev : E->ev_sm) HC(hipEventCreate(&ev));
-    for (auto &ev : E->evx) HC(hipEventCreate(&ev));
+    for (auto &ev : E->ev) HC(hipEventCreate(&ev));
     for (auto &ev : E->ev_grp) HC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     HC(hipHostMalloc((void **)&E->h_vflag, 10 * sizeof(int), hipHostMallocDefault));
     memset(E->h_vflag, 0, 10 * sizeof(int));
     HC(hipHostMalloc((void **)&E->h_lvl, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     for (auto &ev : E->ev_lvl) HC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    for (auto &ev : E->ev_lvlt) HC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HC(hipEventCreate(&E->ev0));
-    HC(hipEventCreate(&E->ev1));
-    HC(hipEventCreate(&E->ev2));
-    HC(hipEventCreate(&E->ev3));
-    HC(hipEventCreate(&E->ev4));
-    HC(hipEventCreate(&E->ev5));
-    HC(hipEventCreate(&E->ev6));
-    HC(hipEventCreate(&E->ev7));
     HC(hipEventCreateWithFlags(&E->ev_snap, hipEventDisableTiming));
     HC(hipEventCreateWithFlags(&E->ev_snap0, hipEventDisableTiming));
     for (auto &ev : E->ev_chunk) HC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -4305,8 +2787,6 @@ void rs_engine_destroy(rs_engine *E) {
   if (E->h_lvl) (void)hipHostFree(E->h_lvl);
   for (auto &ev : E->ev_lvl)
     if (ev) (void)hipEventDestroy(ev);
-  for (auto &ev : E->ev_lvlt)
-    if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : E->ev_grp)
     if (ev) (void)hipEventDestroy(ev);
   for (auto &g : E->kg) g.destroy();
@@ -4316,8 +2796,7 @@ void rs_engine_destroy(rs_engine *E) {
   if (E->ste) (void)hipStreamDestroy(E->ste);
   if (E->stg) (void)hipStreamDestroy(E->stg);
   if (E->srd) (void)hipStreamDestroy(E->srd);
-  for (auto &ev : E->evg)
-    if (ev) (void)hipEventDestroy(ev);
+  if (E->ev_gjoin) (void)hipEventDestroy(E->ev_gjoin);
   for (auto &g : E->evt)
     for (auto &ev : g)
       if (ev) (void)hipEventDestroy(ev);
@@ -4327,14 +2806,6 @@ void rs_engine_destroy(rs_engine *E) {
     if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : E->ev_sm)
     if (ev) (void)hipEventDestroy(ev);
-  if (E->ev0) (void)hipEventDestroy(E->ev0);
-  if (E->ev1) (void)hipEventDestroy(E->ev1);
-  if (E->ev2) (void)hipEventDestroy(E->ev2);
-  if (E->ev3) (void)hipEventDestroy(E->ev3);
-  if (E->ev4) (void)hipEventDestroy(E->ev4);
-  if (E->ev5) (void)hipEventDestroy(E->ev5);
-  if (E->ev6) (void)hipEventDestroy(E->ev6);
-  if (E->ev7) (void)hipEventDestroy(E->ev7);
   if (E->ev_snap) (void)hipEventDestroy(E->ev_snap);
   if (E->ev_snap0) (void)hipEventDestroy(E->ev_snap0);
   for (auto &ev : E->ev_chunk)
@@ -4345,7 +2816,7 @@ void rs_engine_destroy(rs_engine *E) {
   if (E->heap_v) (void)hipFree(E->heap_v);
   if (E->st) (void)hipStreamDestroy(E->st);
   if (E->st2) (void)hipStreamDestroy(E->st2);
-  for (auto &ev : E->evx)
+  for (auto &ev : E->ev)
     if (ev) (void)hipEventDestroy(ev);
   delete E;
 }
@@ -4436,8 +2907,8 @@ static void fetch_result(rs_engine *E, rs_output *o, const std::function<void *(
       const uint64_t tot = E->out_nnz[q];
       L.nnz = tot;
       L.ptr = (uint64_t *)buf(q, 8 * (nd + 1));
-      L.col = (uint32_t *)buf(3 + q, 4 * (tot ? tot : 1));
-      L.val = (uint64_t *)buf(6 + q, 32 * (tot ? tot : 1));
+      L.col = (uint32_t *)buf(kPinCol + q, 4 * (tot ? tot : 1));
+      L.val = (uint64_t *)buf(kPinVal + q, 32 * (tot ? tot : 1));
       *lens[q] = nullptr;
       *jumps[q] = nullptr;
       *njs[q] = 0;
@@ -4452,11 +2923,11 @@ static void fetch_result(rs_engine *E, rs_output *o, const std::function<void *(
     const uint64_t early = E->snap_e[q], ext = E->out_ext[q], nj = E->out_njump[q];
     L.nnz = ext;
     L.ptr = nullptr;  // ABI 8: lengths + jumps (rs_rows_next)
-    *lens[q] = (uint32_t *)pin_get(E, 13 + q, 4 * (nd ? nd : 1));
-    *jumps[q] = (uint64_t *)pin_get(E, q, 8 * (nj ? nj : 1));
+    *lens[q] = (uint32_t *)pin_get(E, kPinLens + q, 4 * (nd ? nd : 1));
+    *jumps[q] = (uint64_t *)pin_get(E, kPinPtr + q, 8 * (nj ? nj : 1));
     *njs[q] = nj;
-    L.col = (uint32_t *)pin_grow_keep(E, 3 + q, 4 * (ext ? ext : 1), 4 * early);
-    L.val = (uint64_t *)pin_grow_keep(E, 6 + q, 32 * (ext ? ext : 1), 32 * early);
+    L.col = (uint32_t *)pin_grow_keep(E, kPinCol + q, 4 * (ext ? ext : 1), 4 * early);
+    L.val = (uint64_t *)pin_grow_keep(E, kPinVal + q, 32 * (ext ? ext : 1), 32 * early);
     if (nd) HC(hipMemcpyAsync(*lens[q], E->A.get<uint32_t>(n + ".len32", 1), 4 * nd, hipMemcpyDeviceToHost, E->st));
     if (nj) HC(hipMemcpyAsync(*jumps[q], E->A.get<uint64_t>(n + ".jtab", 1), 8 * nj, hipMemcpyDeviceToHost, E->st));
     if (ext > early) {
@@ -4466,7 +2937,7 @@ static void fetch_result(rs_engine *E, rs_output *o, const std::function<void *(
     }
   }
   o->n_labels = E->S;
-  o->label_to_wire = (int32_t *)buf(9, 4 * E->S);
+  o->label_to_wire = (int32_t *)buf(kPinL2w, 4 * E->S);
   HC(hipMemcpyAsync(o->label_to_wire, E->A.get<int32_t>("fin.l2w", 1), 4 * E->S, hipMemcpyDeviceToHost, E->st));
   const double tf0 = g_prof_env ? now_ms() : 0.0;
   HC(hipStreamSynchronize(E->st));
@@ -4678,7 +3149,7 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
     hipStream_t st = E->st;
     const uint32_t fs = (uint32_t)field_size_bytes(E->prime);
     const uint64_t n = E->out_n_dev, S = E->S;
-    if (getenv("RS_WRITER_HOST") || n >= (1ull << (64 - kLeKeyBits)) || E->out_nnz[0] >> 32 || E->out_nnz[1] >> 32 || E->out_nnz[2] >> 32) {
+    if (env_flag("RS_WRITER_HOST") || n >= (1ull << (64 - kLeKeyBits)) || E->out_nnz[0] >> 32 || E->out_nnz[1] >> 32 || E->out_nnz[2] >> 32) {
       // the device sort key holds the row in 64 - 36 = 28 bits and the entry index in 32: beyond
       // that, the host writer over the fetched result (same bytes, no such limits)
       rs_output *o = nullptr;
@@ -4773,7 +3244,7 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
     const uint64_t nch = (dev_bytes + kChunk - 1) / kChunk;
     // everything that can throw before the file exists: the pinned buffers, the events (a
     // throw between open() and the guarded block leaked the fd or destroyed joinable threads)
-    uint8_t *pool = nch ? (uint8_t *)pin_get(E, 11, kBufs * kChunk) : nullptr;
+    uint8_t *pool = nch ? (uint8_t *)pin_get(E, kPinWrite, kBufs * kChunk) : nullptr;
     struct Events {
       hipEvent_t e[kBufs] = {};
       ~Events() {
@@ -5067,7 +3538,7 @@ int rs_engine_flatten_dag(rs_engine *E, const rs_dag *dag, const rs_input **in) 
     HC(hipSetDevice(E->device));
     snap_join(E);  // no D2H of an earlier result still reads the engine's buffers
     E->flat_view = rs_input{};
-    flatten_dag(E, dag, &E->flat_view, [E](int slot, size_t bytes) { return pin_get(E, 20 + slot, bytes); });
+    flatten_dag(E, dag, &E->flat_view, [E](int slot, size_t bytes) { return pin_get(E, kPinFlat + slot, bytes); });
     *in = &E->flat_view;
     return RS_OK;
   } catch (const RsError &e) {

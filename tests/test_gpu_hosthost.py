@@ -161,7 +161,7 @@ def test_hosthost_streamed_layout(kind, rows, prime):
 
 @pytest.mark.parametrize("kind,rows,frac", [(0, 400_000, "0.5"), (5, 300_000, "0.2"), (2, 200_000, "0.9")])
 def test_hosthost_first_pass_halves(kind, rows, frac, monkeypatch):
-    """The first frames pass in two parts with a snapshot after each (engine.hip nl_phase / snap_take_h2;
+    """The first frames pass in two parts with a snapshot after each (run.hpp nl_phase / snap_take_h2;
     by default only from 1 M non-linear rows on): forced here on smaller circuits and at other split
     points, the streamed result equals the oracle's on every call, and the off switch gives the same."""
     inp = M.Input.synth(kind, rows, 11, "bn128")

@@ -279,6 +279,20 @@ def test_map_lists_across_rounds(tmp_path):
             assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
 
 
+def test_knobs_parse(tmp_path):
+    """The environment switches' parser (csrc/knobs.hpp): unset gives the default; "0" and "-3" for a
+    knob with min = 1 (RS_SNAP_CHUNK_MB, RS_TAIL_SPLIT: 0 hung the result stream / emptied the first
+    tail group) give 1; "", "abc" give the default; a value above max gives max; a flag is set by any
+    value, the empty one included."""
+    import subprocess
+    root = os.path.dirname(HERE)
+    exe = str(tmp_path / "knobs_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(root, "circom_cvm_amd", "csrc"),
+                           os.path.join(HERE, "knobs_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
+
+
 def test_refcpu_alg_bytes():
     """SURVEY 8(d)'s B_alg as the oracle counts it (refcpu_last_alg; the roofline path's numerator in
     bench.py): deterministic across thread counts, the formula over its terms, Z_in = the input's
