@@ -340,6 +340,10 @@ struct rs_engine {
   };
   hipEvent_t ev_snapq[6] = {};  // the parts' gathers of the first / second snapshot
   hipEvent_t ev_snaph[3] = {};  // the parts' gathers of the first pass's second half
+  // RS_PROF: when the final assembly started / its last kernel was done, when the thread's last copy
+  // was done, and the jobs it had not finished as the assembly started (guarded by snap_m)
+  double asm_t0_ms = 0, asm_end_ms = 0, snap_last_ms = 0;
+  int snap_open = 0, asm_open = 0;
   hipEvent_t ev_fh[2] = {};     // the first pass in halves: first half done / second half starts
   hipEvent_t ev_nlc = nullptr;  // the non-linear blocks' ragged conversion (copy stream) done
   std::mutex snap_m;
@@ -368,6 +372,7 @@ struct rs_engine {
   // the final row views, for the compact CSR built on demand (rs_engine_fetch / the .r1cs writer)
   // when the streamed run skipped it
   bool csr_ready = false;
+  bool csr_rows_ready = false;  // out.{a,b,c}.ptr are built (the fused streamed layout leaves them to ensure_csr)
   // Invariant: these point into arena buffers (sv.*, fin.*, lc.*) and the storage
   // heap as the run left them; nothing between the run and ensure_csr may move them (fin_gen = the
   // arena generation then; ensure_csr refuses a stale view instead of gathering from freed memory).
@@ -748,6 +753,15 @@ static void dev_scan_u64(rs_engine *E, const uint64_t *in, uint64_t *out, uint64
   void *tmp = E->A.get<uint8_t>(std::string("scan.tmp.") + tag, tb);
   HC(rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s));
 }
+// device-only exclusive scan of three columns at once on stream s (no read-back)
+static void dev_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, hipStream_t s, const char *tag) {
+  if (!n) return;
+  size_t tb = 0;
+  const U3 zero{0, 0, 0};
+  HC(rocprim::exclusive_scan(nullptr, tb, in, out, zero, (size_t)n, U3Plus(), s));
+  void *tmp = E->A.get<uint8_t>(std::string("scan3.tmp.") + tag, tb);
+  HC(rocprim::exclusive_scan(tmp, tb, in, out, zero, (size_t)n, U3Plus(), s));
+}
 // device-only exclusive scan of u32 on stream s (no read-back; tmp sized on first use)
 static void dev_scan_u32(rs_engine *E, const uint32_t *in, uint32_t *out, uint64_t n, hipStream_t s, const char *tag) {
   if (!n) return;
@@ -825,16 +839,47 @@ __global__ void k_eq_bf_info(const uint32_t *bf, uint64_t n, const uint64_t *ptr
     for (int t = 0; t < 4; ++t) { o[3 + t] = val ? val[p0].l[t] : 0; o[7 + t] = val ? val[p0 + 1].l[t] : 0; }
   }
 }
-__global__ void k_flag_linear(const uint32_t *la, const uint32_t *lb, uint64_t n, uint64_t *flag_lin, uint64_t *flag_nl) {
-  for (uint64_t i = gtid(); i < n; i += gstride()) {
-    bool lin = la[i] == 0 && lb[i] == 0;
-    flag_lin[i] = lin ? 1 : 0;
-    flag_nl[i] = lin ? 0 : 1;
-  }
-}
 __global__ void k_scatter_ids(const uint64_t *flag, const uint64_t *pos, uint64_t n, uint32_t *ids) {
   for (uint64_t i = gtid(); i < n; i += gstride())
     if (flag[i]) ids[pos[i]] = (uint32_t)i;
+}
+// the split of the non-linear rows from one scan of the linear rows' flags: row i goes to wl[pos[i]]
+// when it turned linear, else to st[i - pos[i]] (both lists ascending)
+__global__ void k_flag_lin(const uint32_t *la, const uint32_t *lb, uint64_t n, uint64_t *flag_lin) {
+  for (uint64_t i = gtid(); i < n; i += gstride()) flag_lin[i] = (la[i] == 0 && lb[i] == 0) ? 1 : 0;
+}
+__global__ void k_split_ids(const uint64_t *flag_lin, const uint64_t *pos, uint64_t n, uint32_t *wl, uint32_t *st) {
+  for (uint64_t i = gtid(); i < n; i += gstride()) {
+    if (flag_lin[i]) wl[pos[i]] = (uint32_t)i;
+    else st[i - pos[i]] = (uint32_t)i;
+  }
+}
+// the compacted views of the storage rows' three parts (rows st_ids) and the C-only view of the rows
+// turned linear (rows wl_ids), and the storage rows' keys marked, in one launch each
+__global__ void k_view_rows4(DRows a, DRows b, DRows c, const uint32_t *st_ids, uint64_t n_st, const uint32_t *wl_ids, uint64_t n_wl,
+                             DRows va, DRows vb, DRows vc, DRows lv) {
+  for (uint64_t i = gtid(); i < n_st + n_wl; i += gstride()) {
+    if (i < n_st) {
+      const uint32_t r = st_ids[i];
+      va.off[i] = a.off[r];
+      va.len[i] = a.len[r];
+      vb.off[i] = b.off[r];
+      vb.len[i] = b.len[r];
+      vc.off[i] = c.off[r];
+      vc.len[i] = c.len[r];
+    } else {
+      const uint32_t r = wl_ids[i - n_st];
+      lv.off[i - n_st] = c.off[r];
+      lv.len[i - n_st] = c.len[r];
+    }
+  }
+}
+__global__ void k_mark_keys3(DRows a, DRows b, DRows c, uint64_t n, uint8_t *bits) {
+  for (uint64_t r = gtid(); r < n; r += gstride()) {
+    for (uint32_t i = 0; i < a.len[r]; ++i) bits[a.key[a.off[r] + i]] = 1;
+    for (uint32_t i = 0; i < b.len[r]; ++i) bits[b.key[b.off[r] + i]] = 1;
+    for (uint32_t i = 0; i < c.len[r]; ++i) bits[c.key[c.off[r] + i]] = 1;
+  }
 }
 __global__ void k_set_rank(const uint32_t *sig, const int32_t *rank, uint64_t n, int32_t *rank_of) {
   for (uint64_t i = gtid(); i < n; i += gstride()) rank_of[sig[i]] = rank[i];
@@ -863,9 +908,6 @@ __global__ void k_unmark_list(const uint32_t *sig, uint64_t n, uint8_t *bits) {
 }
 __global__ void k_zero_c(const uint32_t *ids, uint64_t n, uint32_t *clen) {
   for (uint64_t i = gtid(); i < n; i += gstride()) clen[ids[i]] = 0;
-}
-__global__ void k_nonempty_flags(const uint32_t *la, const uint32_t *lb, const uint32_t *lc, uint64_t n, uint64_t *flag) {
-  for (uint64_t i = gtid(); i < n; i += gstride()) flag[i] = (la[i] | lb[i] | lc[i]) ? 1 : 0;
 }
 
 // (signal, row) pairs of the round-1 storage rows for the flagged signals: the initial lists of
@@ -2479,6 +2521,7 @@ static void snap_join(rs_engine *E) {
   E->snap_cv.notify_all();
   if (E->snap_thread.joinable()) E->snap_thread.join();
   E->snap_q.clear();
+  E->snap_open = 0;
 }
 static void snap_start(rs_engine *E);
 // queues a job, starting the thread when none runs (a run whose first snapshot was empty takes its
@@ -2488,6 +2531,7 @@ static void snap_push(rs_engine *E, const rs_engine::SnapJob &j) {
   {
     std::lock_guard<std::mutex> lk(E->snap_m);
     E->snap_q.push_back(j);
+    ++E->snap_open;
   }
   E->snap_cv.notify_all();
 }
@@ -2528,7 +2572,10 @@ static void snap_start(rs_engine *E) {
       }
       if (g_prof_env) {  // RS_PROF: the link's rate while this job copies (the job is waited for)
         if (hipStreamSynchronize(E->stx) != hipSuccess) E->snap_rc = RS_E_HIP;
-        prof_ms += now_ms() - tj;
+        std::lock_guard<std::mutex> lk(E->snap_m);
+        E->snap_last_ms = now_ms();
+        --E->snap_open;
+        prof_ms += E->snap_last_ms - tj;
         prof_b += j.bytes;
       }
     }
@@ -2579,6 +2626,18 @@ static void ensure_csr(rs_engine *E) {
   hipStream_t st = E->st;
   const char *nm[3] = {"out.a", "out.b", "out.c"};
   const uint64_t n_keep = E->fin_keep, n_out = E->out_n_dev;
+  for (int q = 0; q < 3 && !E->csr_rows_ready; ++q) {  // the rows' lengths and their scan (out_nnz is known)
+    uint64_t *lens = A.get<uint64_t>(std::string(nm[q]) + ".lens", n_out + 1);
+    uint64_t *ptr = A.get<uint64_t>(std::string(nm[q]) + ".ptr", n_out + 1);
+    if (n_keep) launch(st, k_row_lens, n_keep, E->fin_parts[q], E->fin_keep_ids, n_keep, lens);
+    for (int x = 0; x < 2; ++x) {
+      const uint64_t o = n_keep + (x ? E->fin_xn[0] : 0);
+      if (E->fin_xn[x]) launch(st, k_row_lens, E->fin_xn[x], E->fin_xq[x][q], E->fin_x_ids[x], E->fin_xn[x], lens + o);
+    }
+    HC(hipMemsetAsync(lens + n_out, 0, 8, st));
+    dev_scan_u64(E, lens, ptr, n_out + 1, st, nm[q]);
+  }
+  E->csr_rows_ready = true;
   for (int q = 0; q < 3; ++q) {
     const uint64_t tot = E->out_nnz[q];
     const uint64_t *ptr = A.get<uint64_t>(std::string(nm[q]) + ".ptr", n_out + 1);

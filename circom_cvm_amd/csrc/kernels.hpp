@@ -3637,10 +3637,6 @@ __global__ void k_mark_keys(DRows R, uint8_t *bits) {
 __global__ void k_mark_list(const uint32_t *sig, uint64_t n, uint8_t *bits) {
   for (uint64_t i = gtid(); i < n; i += gstride()) bits[sig[i]] = 1;
 }
-// rebuild_witness (:101-124): kept = !deleted && (forbidden || key of non_linear_map)
-__global__ void k_kept(const uint8_t *deleted, const uint8_t *forb, const uint8_t *nlmap, uint32_t *kept, uint64_t S) {
-  for (uint64_t s = gtid(); s < S; s += gstride()) kept[s] = (!deleted[s] && (forb[s] || nlmap[s])) ? 1u : 0u;
-}
 __global__ void k_l2w(const uint32_t *kept, const uint64_t *rank, int32_t *l2w, uint64_t S) {
   for (uint64_t s = gtid(); s < S; s += gstride()) l2w[s] = kept[s] ? (int32_t)rank[s] : -1;
 }

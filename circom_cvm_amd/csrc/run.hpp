@@ -623,24 +623,26 @@ struct Run {
   void snap_take2() {
     if (!E->snap_on || !nl_late || !n_late || (E->comm && E->comm->world > 1)) return;
     HC(hipStreamWaitEvent(st, E->ev_snap, 0));  // the first snapshot's gathers read the flags rewritten here
-    U3 *elen = A.get<U3>("so.elen", n_nl), *eoff2 = A.get<U3>("so.eoff2", n_nl);
+    // (over the list of the pass's rows, nl_lids -- ascending, so the rows land in the same order as a
+    // scan over every non-linear row would put them)
+    U3 *elen = A.get<U3>("so.elen2", n_late), *eoff2 = A.get<U3>("so.eoff2", n_late);
     DRows cp[3];  // copies of the selected rows' views (the rounds re-point rows)
     ViewCopy vc;
     snap_views(stor, "so2.", cp, vc);
-    launch(st, k_snap_lens2, n_nl, stor[0], stor[1], stor[2], (const uint64_t *)nl_late, n_nl, elen, vc);
-    const U3 et = excl_scan_u3(E, elen, eoff2, n_nl, "so2");
+    launch(st, k_snap_lens2_l, n_late, stor[0], stor[1], stor[2], (const uint32_t *)nl_lids, n_late, elen, vc);
+    const U3 et = excl_scan_u3(E, elen, eoff2, n_late, "so2");
     const uint64_t e2[3] = {et.a, et.b, et.c};
     for (int q = 0; q < 3; ++q) E->snap_hint[q] = std::max(E->snap_hint[q], E->snap_e[q] + e2[q]);
     for (int q = 0; q < 3; ++q)
       if (E->snap_e[q] + e2[q] > E->snap_cap[q]) return;  // no room this time (the hint grows the next run's)
-    launch(st, k_snap_mark2, n_nl, (const uint64_t *)nl_late, (const U3 *)elen, (const U3 *)eoff2,
-           U3{E->snap_e[0], E->snap_e[1], E->snap_e[2]}, n_nl, so_early, so_eoff);
+    launch(st, k_snap_mark2_l, n_late, (const uint32_t *)nl_lids, (const U3 *)elen, (const U3 *)eoff2,
+           U3{E->snap_e[0], E->snap_e[1], E->snap_e[2]}, n_late, so_early, so_eoff);
     HC(hipEventRecord(E->ev_snap0, st));
     HC(hipStreamWaitEvent(E->stc, E->ev_snap0, 0));
     snap_tail(e2, E->ev_snapq + 3, "second snapshot", "", [&](int q, uint32_t *col, uint64_t *val, uint64_t) {
-      E->kg[2].run(E->stc, 21 * n_nl + 72 * e2[q], [&] {
-        launch(E->stc, k_snap_gather, n_nl, E->F, cp[q], (const uint8_t *)so_early, (const U3 *)so_eoff, q, n_nl, col, val,
-               (const uint64_t *)nl_late, (uint64_t)0);
+      E->kg[2].run(E->stc, 28 * n_late + 72 * e2[q], [&] {
+        launch(E->stc, k_snap_gather_l, n_late, E->F, cp[q], (const uint32_t *)nl_lids, (const U3 *)elen, (const U3 *)so_eoff, q, n_late,
+               col, val);
       });
     });
   }
@@ -861,16 +863,22 @@ struct Run {
     // split: storage (still non-linear) vs with_linear, both in DFS order
     st_ids = A.get<uint32_t>("st.ids", n_nl);
     wl_ids = A.get<uint32_t>("wl.ids", n_nl);
-    if (n_nl) {
-      uint64_t *fl_lin = A.get<uint64_t>("fl.lin", n_nl), *fl_nl = A.get<uint64_t>("fl.nl", n_nl);
-      uint64_t *p_lin = A.get<uint64_t>("fl.plin", n_nl), *p_nl = A.get<uint64_t>("fl.pnl", n_nl);
-      launch(st, k_flag_linear, n_nl, (const uint32_t *)stor[0].len, (const uint32_t *)stor[1].len, n_nl, fl_lin, fl_nl);
-      n_wl = excl_scan_u64(E, fl_lin, p_lin, n_nl, "fl");
-      n_st = excl_scan_u64(E, fl_nl, p_nl, n_nl, "fn");
-      launch(st, k_scatter_ids, n_nl, (const uint64_t *)fl_lin, (const uint64_t *)p_lin, n_nl, wl_ids);
-      launch(st, k_scatter_ids, n_nl, (const uint64_t *)fl_nl, (const uint64_t *)p_nl, n_nl, st_ids);
+    uint64_t *h_wl = (uint64_t *)pin_get(E, kPinRead, kPinRb);
+    if (n_nl) {  // one scan (of the rows turned linear) places both lists; its total comes back with `bytes`
+      uint64_t *fl_lin = A.get<uint64_t>("fl.lin", n_nl), *p_lin = A.get<uint64_t>("fl.plin", n_nl);
+      uint64_t *d_wl = A.get<uint64_t>("fl.tot", 1);
+      launch(st, k_flag_lin, n_nl, (const uint32_t *)stor[0].len, (const uint32_t *)stor[1].len, n_nl, fl_lin);
+      dev_scan_u64(E, fl_lin, p_lin, n_nl, st, "fl");
+      launch(st, k_scan_total_u64, 1, (const uint64_t *)fl_lin, (const uint64_t *)p_lin, n_nl, d_wl);
+      launch(st, k_split_ids, n_nl, (const uint64_t *)fl_lin, (const uint64_t *)p_lin, n_nl, wl_ids, st_ids);
+      HC(hipMemcpyAsync(h_wl, d_wl, 8, hipMemcpyDeviceToHost, st));
     }
     HC(hipStreamSynchronize(st));
+    if (n_nl) {
+      n_wl = h_wl[0];
+      if (n_wl > n_nl) throw RsError(RS_E_INTERNAL, "non-linear split: row counts out of range");
+      n_st = n_nl - n_wl;
+    }
     E->stats.apply_bytes += bytes;
     if (no_rounds > 0) no_rounds--;
 
@@ -882,21 +890,18 @@ struct Run {
       sv[q].off = A.get<uint64_t>(part_name("sv.", q, ".off"), n_st);
       sv[q].len = A.get<uint32_t>(part_name("sv.", q, ".len"), n_st);
     }
-    if (n_st)
-      for (int q = 0; q < 3; ++q)
-        launch(st, k_view_rows, n_st, (const uint64_t *)stor[q].off, (const uint32_t *)stor[q].len, (const uint32_t *)st_ids, n_st,
-               sv[q].off, sv[q].len);
-    nlmap = A.get<uint8_t>("nlmap", S);
-    HC(hipMemsetAsync(nlmap, 0, S, st));
-    if (n_st)
-      for (const DRows &R : sv) launch(st, k_mark_keys, n_st, R, nlmap);
     // the current linear list: a C-only view
     lv.n = n_wl;
     lv.key = heap_k;
     lv.val = heap_v;
     lv.off = A.get<uint64_t>("lv.off", n_wl);
     lv.len = A.get<uint32_t>("lv.len", n_wl);
-    if (n_wl) launch(st, k_view_rows, n_wl, (const uint64_t *)stor[2].off, (const uint32_t *)stor[2].len, (const uint32_t *)wl_ids, n_wl, lv.off, lv.len);
+    if (n_st + n_wl)
+      launch(st, k_view_rows4, n_st + n_wl, stor[0], stor[1], stor[2], (const uint32_t *)st_ids, n_st, (const uint32_t *)wl_ids, n_wl,
+             sv[0], sv[1], sv[2], lv);
+    nlmap = A.get<uint8_t>("nlmap", S);
+    HC(hipMemsetAsync(nlmap, 0, S, st));
+    if (n_st) launch(st, k_mark_keys3, n_st, sv[0], sv[1], sv[2], n_st, nlmap);
     HC(hipStreamSynchronize(st));
     E->stats.subst_ms += now_ms() - Ts;
     E->stats.nl_ms += now_ms() - Ts;
@@ -1115,7 +1120,11 @@ struct Run {
     launch(st, k_round_count, n_st, ra);
     U3 *rcap3 = A.get<U3>("r.c3", n_st), *rsc3 = A.get<U3>("r.s3", n_st);
     launch(st, k_pack3, n_st, (const uint64_t *)rcap[0], (const uint64_t *)rcap[1], (const uint64_t *)rcap[2], n_st, rcap3);
-    const U3 q3 = excl_scan_u3(E, rcap3, rsc3, n_st, "r");
+    // the touched rows' flags and their scan go along: their count comes back with the capacities' totals
+    uint64_t *tfl = A.get<uint64_t>("r.tfl", n_st), *tfp = A.get<uint64_t>("r.tfp", n_st);
+    launch(st, k_touch_flags, n_st, (const uint64_t *)rcap[2], n_st, tfl);
+    dev_scan_u64(E, tfl, tfp, n_st, st, "tfl");
+    const U3 q3 = n_st ? excl_scan_u3(E, rcap3, rsc3, n_st, "r", tfl + n_st - 1, tfp + n_st - 1, &ra.n_ids) : U3{0, 0, 0};
     const uint64_t qt = q3.a + q3.b + q3.c;
     heap_reserve(qt);
     for (DRows *R : {&sv[0], &sv[1], &sv[2], &lv}) { R->key = heap_k; R->val = heap_v; }
@@ -1135,10 +1144,8 @@ struct Run {
     ra.tmpv = A.get<Fe>("r.tmpv", 2 * (q3.c + 1));
     MK.mark("count");
     {  // compact the touched rows: the fill's lanes all have work
-      uint64_t *tfl = A.get<uint64_t>("r.tfl", n_st), *tfp = A.get<uint64_t>("r.tfp", n_st);
       uint32_t *tids = A.get<uint32_t>("r.touch_ids", n_st);
-      launch(st, k_touch_flags, n_st, (const uint64_t *)rcap[2], n_st, tfl);
-      ra.n_ids = excl_scan_u64(E, tfl, tfp, n_st, "tfl");
+      if (ra.n_ids > n_st) throw RsError(RS_E_INTERNAL, "round: touched rows out of range");
       if (ra.n_ids) launch(st, k_scatter_ids, n_st, (const uint64_t *)tfl, (const uint64_t *)tfp, n_st, tids);
       ra.ids = tids;
       HC(hipMemsetAsync(ra.turn, 0xff, 4 * n_st, st));
@@ -1389,6 +1396,80 @@ struct Run {
     return nn;
   }
 
+  // The streamed layout of a single engine, all three parts per pass (output.hpp, the fused layout):
+  // late lengths -> scan -> extents, ABI 8 lengths and jump flags -> scan -> one read of the totals ->
+  // jump tables and the late rows' gathers.  tots / h_tots: assemble's device words [5..13] and their pinned copy.
+  void assemble_fused(const DRows &lcv, const uint32_t *keep_ids, uint32_t *const (&x_ids)[2], uint64_t n_keep, const uint64_t (&n_x)[2],
+                      uint32_t *zero_len, uint64_t *tots, uint64_t *h_tots) {
+    const char *nm[3] = {"out.a", "out.b", "out.c"};
+    const uint64_t m = n_keep + n_x[0] + n_x[1];
+    OutRows R{};
+    for (int q = 0; q < 3; ++q) {
+      R.st[q] = sv[q];
+      E->fin_parts[q] = sv[q];
+      E->fin_xq[0][q] = lv;
+      E->fin_xq[1][q] = lcv;
+      if (q < 2) E->fin_xq[0][q].len = E->fin_xq[1][q].len = zero_len;
+    }
+    R.xl = lv;
+    R.xc = lcv;
+    R.keep = keep_ids;
+    R.xl_ids = x_ids[0];
+    R.xc_ids = x_ids[1];
+    R.n_keep = n_keep;
+    R.n_xl = n_x[0];
+    R.n_xc = n_x[1];
+    R.nl_of = st_ids;
+    R.early = so_early;
+    R.dirty = so_dirty;
+    R.eoff = so_eoff;
+    R.lc_snap_n = E->lc_snap_n;
+    R.lc_snap_base = E->lc_snap_base;
+    R.base = U3{E->snap_e[0], E->snap_e[1], E->snap_e[2]};
+    U3 *late = A.get<U3>("fin.late3", m), *lptr = A.get<U3>("fin.lptr3", m), *beg = A.get<U3>("fin.beg3", m);
+    U3 *jf = A.get<U3>("fin.jf3", m), *jpos = A.get<U3>("fin.jpos3", m);
+    uint32_t *len32[3];
+    for (int q = 0; q < 3; ++q) len32[q] = A.get<uint32_t>(std::string(nm[q]) + ".len32", m + 1);
+    if (m) {
+      // (capped: its per-wave atomics on three words serialise in the L2 -- 1.7 ms from an uncapped grid of 3 M rows)
+      launch_capped(st, k_out_late3, m, 1024, R, m, late, (unsigned long long *)(tots + 11));
+      dev_scan_u3(E, late, lptr, m, st, "late");
+      launch(st, k_scan_total_u3, 1, (const U3 *)late, (const U3 *)lptr, m, tots + 5);
+      launch(st, k_out_layout3, m, R, m, (const U3 *)lptr, len32[0], len32[1], len32[2], beg, jf);
+      dev_scan_u3(E, jf, jpos, m, st, "jump");
+      launch(st, k_scan_total_u3, 1, (const U3 *)jf, (const U3 *)jpos, m, tots + 8);
+    }
+    HC(hipMemcpyAsync(h_tots + 5, tots + 5, 8 * 9, hipMemcpyDeviceToHost, st));
+    HC(hipStreamSynchronize(st));
+    uint64_t *jtab[3];
+    bool any_j = false;
+    for (int q = 0; q < 3; ++q) {
+      const uint64_t L = h_tots[5 + q], nj = h_tots[8 + q];
+      if (nj > m) throw RsError(RS_E_INTERNAL, "final assembly: jump count out of range");
+      E->out_ext[q] = E->snap_e[q] + L;
+      E->out_njump[q] = nj;
+      E->out_nnz[q] = h_tots[11 + q];
+      jtab[q] = A.get<uint64_t>(std::string(nm[q]) + ".jtab", nj + 1);
+      any_j |= nj != 0;
+    }
+    if (any_j) launch(st, k_out_jtab3, m, (const U3 *)beg, (const U3 *)jf, (const U3 *)jpos, m, jtab[0], jtab[1], jtab[2]);
+    for (int q = 0; q < 3; ++q) {
+      const uint64_t base = E->snap_e[q], ext = E->out_ext[q], L = ext - base;
+      // the device copy of the whole layout grows past the early region when it must (the
+      // early region is copied along once its gather is done)
+      const std::string xc = std::string(nm[q]) + ".xcol", xv = std::string(nm[q]) + ".xval";
+      if (A.cap_bytes(xc) < 4 * ext || A.cap_bytes(xv) < 32 * ext) snap_join(E);  // its D2H reads them
+      A.grow_keep<uint32_t>(xc, ext, base, E->stc, st);
+      A.grow_keep<uint64_t>(xv, 4 * ext, 4 * base, E->stc, st);
+      uint32_t *col = A.get<uint32_t>(xc, ext);
+      uint64_t *val = A.get<uint64_t>(xv, 4 * ext);
+      if (!L) continue;
+      E->kg[2].run(st, 30 * m + 72 * L, [&] {
+        launch(st, k_gather_late_all, m, E->F, R, q, m, (const U3 *)lptr, col + base, val + 4 * base);
+      });
+    }
+  }
+
   // ======================= final assembly (:648-729)
   // Reads sv, lv, lc, nlmap, the bitmaps, st_ids and the streamed-output state (so_early,
   // so_eoff, so_dirty, snap_e).  Leaves in the engine: the witness map (n_wires, npiw, fin.l2w), the
@@ -1396,6 +1477,12 @@ struct Run {
   // every row's extent (out_ext, out_njump); else the compact CSR.
   void assemble() {
     Tf = now_ms();
+    if (g_prof_env) {  // how far the result stream is as the assembly starts (after the device caught up)
+      HC(hipStreamSynchronize(st));
+      std::lock_guard<std::mutex> lk(E->snap_m);
+      E->asm_t0_ms = now_ms();
+      E->asm_open = E->snap_open;
+    }
     // leftover linear rows (rounds exhausted) and lconst: appended after the storage rows; their
     // signals join the non-linear map (:648-686)
     const DRows lcv = lc.view(A);
@@ -1406,60 +1493,63 @@ struct Run {
     uint64_t *kept64 = A.get<uint64_t>("fin.kept64", S);
     uint64_t *rank = A.get<uint64_t>("fin.rank", S);
     int32_t *l2w = A.get<int32_t>("fin.l2w", S);
-    launch(st, k_kept, S, (const uint8_t *)d_deleted, (const uint8_t *)d_forb, (const uint8_t *)nlmap, kept, S);
-    launch(st, k_u32_to_u64, S, (const uint32_t *)kept, kept64, S);
-    E->n_wires = excl_scan_u64(E, kept64, rank, S, "kept");
+    // every total of this phase is left in one block of device words and read in two copies (two
+    // synchronisations): [0] wires [1] inputs not kept [2] kept storage rows [3..4] non-empty extras,
+    // then (single engine, streamed) [5..7] late entries [8..10] jumps [11..13] entries per part
+    uint64_t *tots = A.get<uint64_t>("fin.tots", 14);
+    uint64_t *h_tots = (uint64_t *)pin_get(E, kPinRead, kPinRb);
+    HC(hipMemsetAsync(tots, 0, 8 * 14, st));
+    launch(st, k_kept_count, S, (const uint8_t *)d_deleted, (const uint8_t *)d_forb, (const uint8_t *)nlmap, kept, kept64, S,
+           E->n_pub_out + 1, E->n_pub_out + E->n_pub_in + E->n_priv_in, (unsigned long long *)(tots + 1));
+    dev_scan_u64(E, kept64, rank, S, st, "kept");
+    launch(st, k_scan_total_u64, 1, (const uint64_t *)kept64, (const uint64_t *)rank, S, tots + 0);
     launch(st, k_l2w, S, (const uint32_t *)kept, (const uint64_t *)rank, l2w, S);
-    {
-      uint64_t lo = E->n_pub_out + 1, hi = E->n_pub_out + E->n_pub_in + E->n_priv_in;
-      uint64_t del_in = 0;
-      if (hi >= lo && lo < S) {
-        uint64_t cnt = std::min<uint64_t>(hi, S - 1) - lo + 1;
-        std::vector<uint32_t> k(cnt);
-        HC(hipMemcpyAsync(k.data(), kept + lo, 4 * cnt, hipMemcpyDeviceToHost, st));
-        HC(hipStreamSynchronize(st));
-        for (uint32_t x : k) del_in += x ? 0 : 1;
-      }
-      E->npiw = E->n_priv_in - del_in;
-    }
+    Comm *CMf = E->comm.get();
+    const bool shard = E->snap_on && CMf && CMf->world > 1;
+    const bool fused = E->snap_on && !shard;  // single engine, streamed: the fused layout
     // output rows: storage (non-empty) ++ leftover linear ++ lconst, empty rows dropped
     // (extract_with(is_empty), :697); the last two are C-only ("extras")
     {
-      uint64_t *nef = A.get<uint64_t>("fin.nef", n_st), *nep = A.get<uint64_t>("fin.nep", n_st);
-      uint64_t n_keep = 0;
-      if (n_st) {
-        launch(st, k_nonempty_flags, n_st, (const uint32_t *)sv[0].len, (const uint32_t *)sv[1].len, (const uint32_t *)sv[2].len, n_st, nef);
-        n_keep = excl_scan_u64(E, nef, nep, n_st, "ne");
-      }
-      uint32_t *keep_ids = A.get<uint32_t>("fin.keep", n_keep);
-      if (n_keep) launch(st, k_scatter_ids, n_st, (const uint64_t *)nef, (const uint64_t *)nep, n_st, keep_ids);
       const DRows xsrc[2] = {lv, lcv};
+      uint64_t *nef = A.get<uint64_t>("fin.nef", n_st), *nep = A.get<uint64_t>("fin.nep", n_st);
+      uint64_t *xf[2], *xp[2];
+      for (int x = 0; x < 2; ++x) {
+        xf[x] = A.get<uint64_t>(x ? "fin.xf1" : "fin.xf0", xsrc[x].n);
+        xp[x] = A.get<uint64_t>(x ? "fin.xp1" : "fin.xp0", xsrc[x].n);
+      }
+      const uint64_t n_cand = n_st + lv.n + lcv.n;
+      if (n_cand) launch(st, k_nonempty_flags3, n_cand, sv[0], sv[1], sv[2], n_st, lv, lcv, nef, xf[0], xf[1]);
+      dev_scan_u64(E, nef, nep, n_st, st, "ne");
+      launch(st, k_scan_total_u64, 1, (const uint64_t *)nef, (const uint64_t *)nep, n_st, tots + 2);
+      for (int x = 0; x < 2; ++x) {
+        dev_scan_u64(E, xf[x], xp[x], xsrc[x].n, st, x ? "xf1" : "xf0");
+        launch(st, k_scan_total_u64, 1, (const uint64_t *)xf[x], (const uint64_t *)xp[x], xsrc[x].n, tots + 3 + x);
+      }
+      HC(hipMemcpyAsync(h_tots, tots, 8 * 5, hipMemcpyDeviceToHost, st));
+      HC(hipStreamSynchronize(st));
+      E->n_wires = h_tots[0];
+      E->npiw = E->n_priv_in - h_tots[1];
+      const uint64_t n_keep = h_tots[2];
+      uint64_t n_x[2] = {h_tots[3], h_tots[4]}, x_at[2];
+      uint32_t *keep_ids = A.get<uint32_t>("fin.keep", n_keep);
+      uint32_t *x_ids[2] = {A.get<uint32_t>("fin.lvids", lv.n), A.get<uint32_t>("fin.lcids", lcv.n)};
+      if (n_keep > n_st || n_x[0] > lv.n || n_x[1] > lcv.n) throw RsError(RS_E_INTERNAL, "final assembly: row counts out of range");
+      if (n_cand)
+        launch(st, k_scatter_ids3, n_cand, (const uint64_t *)nef, (const uint64_t *)nep, n_st, (const uint64_t *)xf[0],
+               (const uint64_t *)xp[0], lv.n, (const uint64_t *)xf[1], (const uint64_t *)xp[1], lcv.n, keep_ids, x_ids[0], x_ids[1]);
       const uint64_t zn = std::max<uint64_t>(lv.n, lcv.n);
       uint32_t *zero_len = A.get<uint32_t>("fin.zlen", zn);
       if (zn) HC(hipMemsetAsync(zero_len, 0, 4 * zn, st));
-      uint32_t *x_ids[2];
-      uint64_t n_x[2] = {0, 0}, x_at[2];
-      for (int x = 0; x < 2; ++x) {
-        const DRows &V = xsrc[x];
-        x_ids[x] = A.get<uint32_t>(x ? "fin.lcids" : "fin.lvids", V.n);
-        if (!V.n) continue;
-        uint64_t *lf = A.get<uint64_t>("fin.xf", V.n), *lp = A.get<uint64_t>("fin.xp", V.n);
-        launch(st, k_nonempty_flags, V.n, (const uint32_t *)zero_len, (const uint32_t *)zero_len, (const uint32_t *)V.len, V.n, lf);
-        n_x[x] = excl_scan_u64(E, lf, lp, V.n, "xf");
-        launch(st, k_scatter_ids, V.n, (const uint64_t *)lf, (const uint64_t *)lp, V.n, x_ids[x]);
-      }
       x_at[0] = n_keep;
       x_at[1] = n_keep + n_x[0];
       const uint64_t n_out = n_keep + n_x[0] + n_x[1];
-      if (n_keep > n_st || n_x[0] > lv.n || n_x[1] > lcv.n) throw RsError(RS_E_INTERNAL, "final assembly: row counts out of range");
       E->out_n_dev = n_out;
       const DRows *parts[3] = {&sv[0], &sv[1], &sv[2]};
       const char *nm[3] = {"out.a", "out.b", "out.c"};
+      if (fused) assemble_fused(lcv, keep_ids, x_ids, n_keep, n_x, zero_len, tots, h_tots);
       // the streamed layout covers this engine's rows: all of them, or sharded its share -- the kept
       // storage rows of its non-linear rows (a run [k_lo, k_hi) of the keep list), the last rank also
       // the two C-only tails
-      Comm *CMf = E->comm.get();
-      const bool shard = E->snap_on && CMf && CMf->world > 1;
       uint64_t k_lo = 0, k_hi = n_keep;
       bool with_x = true;
       if (shard) {
@@ -1481,7 +1571,8 @@ struct Run {
       const uint64_t xl_at[2] = {own, own + (with_x ? n_x[0] : 0)};
       const uint64_t xl_n[2] = {with_x ? n_x[0] : 0, with_x ? n_x[1] : 0};
       const uint64_t m_loc = own + xl_n[0] + xl_n[1];
-      for (int q = 0; q < 3; ++q) {
+      E->csr_rows_ready = !fused;  // (the fused layout leaves the compact CSR's row pointers to ensure_csr)
+      for (int q = 0; q < 3 && !fused; ++q) {  // not streamed, or sharded: one part at a time
         uint64_t *lens = A.get<uint64_t>(std::string(nm[q]) + ".lens", n_out + 1);
         uint64_t *ptr = A.get<uint64_t>(std::string(nm[q]) + ".ptr", n_out + 1);
         if (n_keep) launch(st, k_row_lens, n_keep, *parts[q], (const uint32_t *)keep_ids, n_keep, lens);
@@ -1574,6 +1665,14 @@ struct Run {
       }
       E->fin_gen = A.gen;
       if (!E->snap_on) ensure_csr(E);
+    }
+    if (g_prof_env) {
+      HC(hipStreamSynchronize(st));
+      std::lock_guard<std::mutex> lk(E->snap_m);
+      E->asm_end_ms = now_ms();
+      fprintf(stderr, "[rs-prof] final assembly: %.2f ms (device done); the result stream had %d copies unfinished at its start, "
+                      "%d at its end (its last copy was done %.2f ms before the end)\n",
+              E->asm_end_ms - E->asm_t0_ms, E->asm_open, E->snap_open, E->asm_end_ms - E->snap_last_ms);
     }
   }
 
