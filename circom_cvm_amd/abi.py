@@ -127,7 +127,9 @@ class RsStats(C.Structure):
                 ("check_ms", C.c_double), ("check_bytes", C.c_uint64), ("check_launches", C.c_uint64),
                 ("ragged_ms", C.c_double), ("ragged_bytes", C.c_uint64), ("ragged_launches", C.c_uint64),
                 ("gather_ms", C.c_double), ("gather_bytes", C.c_uint64), ("gather_launches", C.c_uint64),
-                ("cluster_host_ms", C.c_double)]
+                ("cluster_host_ms", C.c_double),
+                ("read_ms", C.c_double), ("read_upload_ms", C.c_double), ("read_kernel_ms", C.c_double),
+                ("read_d2h_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -182,6 +184,8 @@ SYMBOLS = [
     ("rs_synth", C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(RsInput))]),
     ("rs_flatten_dag", C.c_int, [C.c_int, C.POINTER(RsDag), C.POINTER(C.POINTER(RsInput))]),
     ("rs_engine_flatten_dag", C.c_int, [C.c_void_p, C.POINTER(RsDag), C.POINTER(C.POINTER(RsInput))]),
+    ("rs_engine_read_r1cs_o0", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(RsInput))]),
+    ("rs_read_r1cs_o0_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.POINTER(RsInput))]),
 ]
 
 _LIB = None
@@ -308,9 +312,17 @@ class Engine:
 
     def flatten_dag(self, dag) -> RsInput:
         """rs_engine_flatten_dag: `dag` (circom_cvm_amd.Dag) flattened into this engine's page-locked
-        buffers; the returned struct views them until the next flatten_dag on this engine."""
+        buffers; the returned struct views them until the next flatten_dag or read_r1cs on this engine."""
         p = C.POINTER(RsInput)()
         check(lib().rs_engine_flatten_dag(self._h, C.byref(dag.c), C.byref(p)))
+        return p.contents
+
+    def read_r1cs(self, path: str) -> RsInput:
+        """rs_engine_read_r1cs_o0: the --O0 file read and classified on the device into this engine's
+        page-locked buffers (the ones flatten_dag uses); the returned struct views them until the next
+        read_r1cs or flatten_dag on this engine."""
+        p = C.POINTER(RsInput)()
+        check(lib().rs_engine_read_r1cs_o0(self._h, path.encode(), C.byref(p)))
         return p.contents
 
     def inject_fault(self, where: int = 1):
@@ -375,6 +387,13 @@ class Input:
     def read_r1cs(path: str) -> "Input":
         p = C.POINTER(RsInput)()
         check(lib().rs_read_r1cs_o0(path.encode(), C.byref(p)))
+        return Input(p)
+
+    @staticmethod
+    def read_r1cs_device(path: str, device: int = 0) -> "Input":
+        """rs_read_r1cs_o0_device: the same result as read_r1cs, read and classified on the GPU."""
+        p = C.POINTER(RsInput)()
+        check(lib().rs_read_r1cs_o0_device(device, path.encode(), C.byref(p)))
         return Input(p)
 
     @staticmethod

@@ -2,13 +2,17 @@
 //
 //   circom-simplify <in_O0.r1cs> [<in_O0.sym>] --O1|--O2|--O2round N
 //                   [--use_old_simplification_heuristics] [--json] [--simplification_substitution]
-//                   [--device D] -o <out_prefix>
+//                   [--device D] [--host-reader] -o <out_prefix>
 //
 // Reads an --O0 export (which losslessly holds what simplification() consumes, SURVEY CS-4),
 // runs the GPU back end and writes <out_prefix>.r1cs (+ .sym), like `circom --r1cs --sym` at the
 // given level (circom/src/input_user.rs:286-306 for the flag semantics); --json adds
 // <out_prefix>_constraints.json and --simplification_substitution <out_prefix>_substitutions.json
 // (the file names circom derives from its output base, input_user.rs).
+//
+// The --O0 file is read and classified on the device (rs_engine_read_r1cs_o0) and simplified on the
+// same engine (rs_engine_simplify); --host-reader reads it with rs_read_r1cs_o0 and runs the one-shot
+// rs_simplify instead.  The files and the summary are the same bytes either way.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -20,7 +24,7 @@
 int main(int argc, char **argv) {
   const char *in_r1cs = nullptr, *in_sym = nullptr;
   std::string out;
-  bool json = false;
+  bool json = false, host_reader = false;
   rs_flags fl;
   memset(&fl, 0, sizeof(fl));
   fl.flag_s = 1;  // --O1 is circom's default since 2.2.0 (input_user.rs:304)
@@ -35,6 +39,7 @@ int main(int argc, char **argv) {
       else { fl.flag_s = 0; fl.no_rounds = n; }
     } else if (a == "--use_old_simplification_heuristics") fl.use_old_heuristics = 1;
     else if (a == "--json") json = true;
+    else if (a == "--host-reader") host_reader = true;
     else if (a == "--simplification_substitution") fl.emit_substitution_log = 1;
     else if (a == "--device" && i + 1 < argc) fl.device = atoi(argv[++i]);
     else if (a == "-o" && i + 1 < argc) out = argv[++i];
@@ -44,16 +49,33 @@ int main(int argc, char **argv) {
   }
   if (!in_r1cs || out.empty()) {
     fprintf(stderr, "usage: circom-simplify in_O0.r1cs [in_O0.sym] --O1|--O2|--O2round N [--json] "
-                    "[--simplification_substitution] -o out_prefix\n");
+                    "[--simplification_substitution] [--host-reader] -o out_prefix\n");
     return 2;
   }
-  rs_input *in = nullptr;
-  if (rs_read_r1cs_o0(in_r1cs, &in)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
-  rs_output *o = nullptr;
-  auto t0 = std::chrono::steady_clock::now();
-  int rc = rs_simplify(in, &fl, &o);
-  auto t1 = std::chrono::steady_clock::now();
-  if (rc) { fprintf(stderr, "error %d: %s\n", rc, rs_last_error()); rs_input_free(in); return 1; }
+  // (`in` and `o` are the library's either way: owned by the engine, or freed below)
+  const rs_input *in = nullptr;
+  const rs_output *o = nullptr;
+  rs_input *in_own = nullptr;
+  rs_output *o_own = nullptr;
+  rs_engine *eng = nullptr;
+  std::chrono::steady_clock::time_point t0, t1;
+  if (host_reader) {
+    if (rs_read_r1cs_o0(in_r1cs, &in_own)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
+    in = in_own;
+    t0 = std::chrono::steady_clock::now();
+    int rc = rs_simplify(in, &fl, &o_own);
+    t1 = std::chrono::steady_clock::now();
+    if (rc) { fprintf(stderr, "error %d: %s\n", rc, rs_last_error()); rs_input_free(in_own); return 1; }
+    o = o_own;
+  } else {
+    int rc = rs_engine_create(fl.device, &eng);
+    if (!rc) rc = rs_engine_read_r1cs_o0(eng, in_r1cs, &in);
+    if (rc) { fprintf(stderr, "error: %s\n", rs_last_error()); rs_engine_destroy(eng); return 1; }
+    t0 = std::chrono::steady_clock::now();
+    rc = rs_engine_simplify(eng, in, &fl, &o);
+    t1 = std::chrono::steady_clock::now();
+    if (rc) { fprintf(stderr, "error %d: %s\n", rc, rs_last_error()); rs_engine_destroy(eng); return 1; }
+  }
   if (rs_write_r1cs_gates((out + ".r1cs").c_str(), in, o, in_r1cs)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
   if (in_sym && rs_write_sym(in_sym, (out + ".sym").c_str(), o)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
   if (json && rs_write_constraints_json((out + "_constraints.json").c_str(), o)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
@@ -86,7 +108,8 @@ int main(int argc, char **argv) {
   printf("wires: %llu\n", (unsigned long long)o->n_wires);
   printf("labels: %llu\n", (unsigned long long)o->n_labels);
   fprintf(stderr, "simplification: %.3f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count());
-  rs_output_free(o);
-  rs_input_free(in);
+  rs_output_free(o_own);
+  rs_input_free(in_own);
+  rs_engine_destroy(eng);
   return 0;
 }

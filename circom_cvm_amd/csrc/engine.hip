@@ -244,7 +244,8 @@ enum PinSlot {
   kPinReplayStage = 17,
   kPinRead = 18,         // small read-backs (kPinRb bytes, never reallocated)
   kPinCluster = 19,      // the clustering's read-back
-  kPinFlat = 20,         // rs_engine_flatten_dag's result (19 arrays)
+  kPinFlat = 20,         // rs_engine_flatten_dag's / rs_engine_read_r1cs_o0's result (19 arrays)
+  kPinStage = 39,        // rs_engine_read_r1cs_o0's staging pool (the constraint section on its way up)
   kPinCount = 40
 };
 
@@ -306,7 +307,7 @@ struct rs_engine {
     size_t cap = 0;
   };
   Pin pin[kPinCount];    // (enum PinSlot)
-  rs_input flat_view{};  // rs_engine_flatten_dag's result (views pin[kPinFlat + 0..18])
+  rs_input flat_view{};  // rs_engine_flatten_dag's or rs_engine_read_r1cs_o0's result, whichever ran last (views pin[kPinFlat + 0..18])
   rs_output view{};
   // streamed result (output.hpp; rs_engine_simplify): the storage rows final after round 1 go to
   // pin[3..8] on the copy stream during the later rounds (ev_snap: their D2H is done)
@@ -703,6 +704,7 @@ static U3 excl_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, const ch
   return n ? U3{h[0] + h[3], h[1] + h[4], h[2] + h[5]} : U3{0, 0, 0};
 }
 #include "flatten.hpp"
+#include "r1cs_read.hpp"
 #include "output.hpp"
 __global__ void k_pack3(const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n, U3 *out) {
   for (uint64_t i = gtid(); i < n; i += gstride()) out[i] = U3{a[i], b[i], c[i]};
@@ -3598,6 +3600,58 @@ int rs_engine_flatten_dag(rs_engine *E, const rs_dag *dag, const rs_input **in) 
     snap_join(E);  // no D2H of an earlier result still reads the engine's buffers
     E->flat_view = rs_input{};
     flatten_dag(E, dag, &E->flat_view, [E](int slot, size_t bytes) { return pin_get(E, kPinFlat + slot, bytes); });
+    *in = &E->flat_view;
+    return RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    return RS_E_INTERNAL;
+  }
+}
+
+// The device --O0 reader (r1cs_read.hpp).  The one-shot: malloc'ed arrays like rs_read_r1cs_o0's.
+int rs_read_r1cs_o0_device(int device, const char *path, rs_input **in) {
+  if (!path || !in) { set_error("rs_read_r1cs_o0_device: null argument"); return RS_E_INVALID; }
+  *in = nullptr;
+  rs_engine *E = nullptr;
+  int rc = rs_engine_create(device, &E);
+  if (rc) return rc;
+  rs_input *o = (rs_input *)calloc(1, sizeof(rs_input));
+  try {
+    HC(hipSetDevice(E->device));
+    read_r1cs_device(E, path, o, [](int, size_t bytes) {
+      void *p = malloc(bytes ? bytes : 1);
+      if (!p) throw std::bad_alloc();
+      return p;
+    });
+    *in = o;
+    o = nullptr;
+    rc = RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    rc = e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    rc = RS_E_INTERNAL;
+  }
+  if (o) rs_input_free(o);  // a failed call: the arrays made so far (calloc'ed struct: NULL elsewhere)
+  rs_engine_destroy(E);
+  return rc;
+}
+
+// On a persistent engine, into the page-locked buffers rs_engine_flatten_dag's result uses too
+// (flat_view, pin[kPinFlat..]): *in is valid until the next read or flatten on `eng`.
+int rs_engine_read_r1cs_o0(rs_engine *E, const char *path, const rs_input **in) {
+  if (!E || !path || !in) { set_error("rs_engine_read_r1cs_o0: null argument"); return RS_E_INVALID; }
+  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (the reader thread inherits it)
+  *in = nullptr;
+  try {
+    HC(hipSetDevice(E->device));
+    snap_join(E);  // no D2H of an earlier result still reads the engine's buffers
+    E->flat_view = rs_input{};
+    read_r1cs_device(E, path, &E->flat_view, [E](int slot, size_t bytes) { return pin_get(E, kPinFlat + slot, bytes); });
     *in = &E->flat_view;
     return RS_OK;
   } catch (const RsError &e) {

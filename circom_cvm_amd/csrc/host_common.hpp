@@ -68,6 +68,27 @@ inline void to_lc(Block &b, rs_lc &lc) {
 bool r1cs_gate_sections(const char *o0_r1cs, const int32_t *l2w, uint64_t n_labels, std::vector<uint8_t> &out,
                         bool &present);
 
+// Section table of an .r1cs file (r1cs_writer.rs:147-204): the first section of each type 1-5.
+struct R1csSections {
+  bool have[6] = {};
+  uint64_t off[6] = {}, size[6] = {};
+};
+// What an --O0 file's small sections say (header, custom gates): everything of the rs_input but the
+// six blocks.
+struct R1csO0Head {
+  uint32_t fs = 0;  // bytes of a field element in the file: 8, 16, 24 or 32
+  uint64_t prime[4] = {0, 0, 0, 0};
+  uint32_t prime_id = RS_PRIME_CUSTOM;
+  uint32_t n_out = 0, n_pub = 0, n_prv = 0, n_cons = 0;
+  uint64_t n_labels = 0;
+  std::vector<uint32_t> forbidden;  // sorted, distinct
+};
+// r1cs_io.cpp: the small sections parsed (each given alone; s4 / s5 nullptr when absent), and an --O0
+// file opened through preads of the section table and those sections only (the caller closes *fd)
+bool r1cs_o0_small(const uint8_t *s1, uint64_t size1, const uint8_t *s4, uint64_t size4, const uint8_t *s5, uint64_t size5,
+                   R1csO0Head &H);
+bool r1cs_o0_open(const char *path, int *fd, R1csSections &S, R1csO0Head &H);
+
 inline void free_lc(rs_lc &lc) {
   free(lc.ptr);
   free(lc.col);

@@ -16,6 +16,10 @@
 #include <fstream>
 #include <sstream>
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include "host_common.hpp"
 
 namespace rs {
@@ -61,16 +65,17 @@ static inline uint64_t le_order_key(uint32_t k) {
   return key;
 }
 
-// Bounds-checked reader over one section [off, off + size) of an .r1cs buffer: every read fails
-// (with the error set) instead of running past the section or the file.
+// Bounds-checked reader over one section [off, off + size) of an .r1cs buffer (the whole file, or the
+// section alone with off = 0): every read fails (with the error set) instead of running past the
+// section or the file.
 struct Cursor {
-  const std::vector<uint8_t> &b;
+  const uint8_t *b;
   uint64_t pos, end;
-  Cursor(const std::vector<uint8_t> &buf, uint64_t off, uint64_t size) : b(buf), pos(off), end(off + size) {}
+  Cursor(const uint8_t *buf, uint64_t off, uint64_t size) : b(buf), pos(off), end(off + size) {}
   uint64_t left() const { return end - pos; }
   bool bytes(void *dst, uint64_t n) {
     if (n > left()) { set_error("truncated r1cs section"); return false; }
-    memcpy(dst, &b[pos], n);
+    memcpy(dst, b + pos, n);
     pos += n;
     return true;
   }
@@ -84,30 +89,35 @@ struct Cursor {
 };
 
 // Section table of an .r1cs file (r1cs_writer.rs:147-204): the first section of each type 1-5.
-struct R1csSections {
-  bool have[6] = {};
-  uint64_t off[6] = {}, size[6] = {};
-};
-static bool scan_sections(const std::vector<uint8_t> &buf, R1csSections &S) {
-  uint32_t nsec = rd<uint32_t>(&buf[8]);
+// (R1csSections: host_common.hpp.)  read_at(off, dst, n) copies n bytes of the file at off (the
+// caller has checked off + n <= file_size): the file in memory, or preads of the table's entries.
+template <class ReadAt>
+static bool scan_sections(ReadAt &&read_at, uint64_t file_size, R1csSections &S) {
+  uint32_t nsec = 0;
+  if (!read_at(8, &nsec, 4)) { set_error("cannot read the r1cs section table"); return false; }
   uint64_t off = 12;
   for (uint32_t s = 0; s < nsec; ++s) {
-    if (off + 12 > buf.size()) { set_error("truncated r1cs section table"); return false; }
-    const uint32_t t = rd<uint32_t>(&buf[off]);
-    const uint64_t sz = rd<uint64_t>(&buf[off + 4]);
+    if (off + 12 > file_size) { set_error("truncated r1cs section table"); return false; }
+    uint8_t e[12];
+    if (!read_at(off, e, 12)) { set_error("cannot read the r1cs section table"); return false; }
+    const uint32_t t = rd<uint32_t>(e);
+    const uint64_t sz = rd<uint64_t>(e + 4);
     off += 12;
-    if (sz > buf.size() - off) { set_error("r1cs section runs past the end of the file"); return false; }
+    if (sz > file_size - off) { set_error("r1cs section runs past the end of the file"); return false; }
     if (t >= 1 && t <= 5 && !S.have[t]) { S.have[t] = true; S.off[t] = off; S.size[t] = sz; }
     off += sz;
   }
   return true;
 }
+static bool scan_sections(const std::vector<uint8_t> &buf, R1csSections &S) {
+  return scan_sections([&](uint64_t off, void *dst, size_t n) { memcpy(dst, &buf[off], n); return true; }, buf.size(), S);
+}
 // Custom gates applied (section 5, r1cs_writer.rs:408-450): u32 count, then per application a u32
 // gate index, a u32 signal count and u64 signals.  Collects the signals (sorted, distinct) and/or
 // the raw applications.
-static bool read_gate_applications(const std::vector<uint8_t> &buf, const R1csSections &S, uint64_t n_labels,
+static bool read_gate_applications(const uint8_t *sec5, uint64_t size5, uint64_t n_labels,
                                    std::vector<uint32_t> *sigs, std::vector<std::pair<uint32_t, std::vector<uint64_t>>> *apps) {
-  Cursor c(buf, S.off[5], S.size[5]);
+  Cursor c(sec5, 0, size5);
   uint32_t na = 0;
   if (!c.u32(na)) return false;
   for (uint32_t a = 0; a < na; ++a) {
@@ -126,6 +136,105 @@ static bool read_gate_applications(const std::vector<uint8_t> &buf, const R1csSe
     std::sort(sigs->begin(), sigs->end());
     sigs->erase(std::unique(sigs->begin(), sigs->end()), sigs->end());
   }
+  return true;
+}
+
+// The small sections of an --O0 file, each given alone (s4 / s5: nullptr when absent): the header
+// (section 1), the custom gates used (4, checked for shape only) and applied (5, whose signals join
+// `forbidden`).  Both --O0 readers parse them here: rs_read_r1cs_o0 from the file in memory, the device
+// reader from preads of just these sections.
+bool r1cs_o0_small(const uint8_t *s1, uint64_t size1, const uint8_t *s4, uint64_t size4, const uint8_t *s5, uint64_t size5,
+                   R1csO0Head &H) {
+  Cursor hc(s1, 0, size1);
+  uint32_t fs = 0;
+  if (!hc.u32(fs)) return false;
+  if (fs == 0 || fs > 32 || fs % 8) { set_error("unsupported field size"); return false; }
+  uint64_t p[4] = {0, 0, 0, 0};
+  uint32_t n_wires = 0, n_out = 0, n_pub = 0, n_prv = 0, n_cons = 0;
+  uint64_t n_labels = 0;
+  if (!hc.bytes(p, fs) || !hc.u32(n_wires) || !hc.u32(n_out) || !hc.u32(n_pub) || !hc.u32(n_prv) ||
+      !hc.u64(n_labels) || !hc.u32(n_cons))
+    return false;
+  if (n_labels == 0 || n_labels > 0x7fffffffull || 1 + (uint64_t)n_out + n_pub > n_labels) {
+    set_error("r1cs header: bad label count");
+    return false;
+  }
+  // custom-gate signals (section 5, written by dag/src/r1cs_porting.rs:74-107) are forbidden:
+  // map_tree inserts every signal of a custom-gate node (dag/src/map_to_constraint_list.rs:22-24)
+  std::vector<uint32_t> gate_sigs;
+  if (s5 && !read_gate_applications(s5, size5, n_labels, &gate_sigs, nullptr)) return false;
+  if (s4) {  // custom gates used (r1cs_writer.rs:358-405): checked for shape only
+    Cursor gc(s4, 0, size4);
+    uint32_t ng = 0;
+    if (!gc.u32(ng)) return false;
+    for (uint32_t g = 0; g < ng; ++g) {
+      uint8_t ch = 1;
+      while (ch != 0)
+        if (!gc.bytes(&ch, 1)) return false;
+      uint32_t np = 0;
+      if (!gc.u32(np) || !gc.skip((uint64_t)np * fs)) return false;
+    }
+  }
+
+  // forbidden_if_main = {0} u outputs u public inputs (dag/src/lib.rs:174, 179-204) u custom-gate
+  // signals, sorted and distinct
+  std::vector<uint32_t> &forb = H.forbidden;
+  forb.clear();
+  forb.reserve(1 + (uint64_t)n_out + n_pub + gate_sigs.size());
+  for (uint64_t i = 0; i < 1 + (uint64_t)n_out + n_pub; ++i) forb.push_back((uint32_t)i);
+  forb.insert(forb.end(), gate_sigs.begin(), gate_sigs.end());
+  std::sort(forb.begin(), forb.end());
+  forb.erase(std::unique(forb.begin(), forb.end()), forb.end());
+  H.fs = fs;
+  memcpy(H.prime, p, 32);
+  H.prime_id = RS_PRIME_CUSTOM;
+  for (int i = 0; i < 8; ++i)
+    if (memcmp(kPrimes[i], p, 32) == 0) H.prime_id = i;
+  H.n_out = n_out;
+  H.n_pub = n_pub;
+  H.n_prv = n_prv;
+  H.n_cons = n_cons;
+  H.n_labels = n_labels;
+  return true;
+}
+
+// Opens an --O0 file for the device reader: the section table and the small sections through preads
+// (never the constraint section's bytes), with rs_read_r1cs_o0's checks.  The caller closes *fd.
+bool r1cs_o0_open(const char *path, int *fd_out, R1csSections &S, R1csO0Head &H) {
+  *fd_out = -1;
+  const int fd = open(path, O_RDONLY);
+  struct stat sb;
+  uint8_t magic[12];
+  auto read_at = [fd](uint64_t off, void *dst, size_t n) {
+    uint8_t *d = (uint8_t *)dst;
+    while (n) {
+      const ssize_t g = pread(fd, d, n, (off_t)off);
+      if (g <= 0) return false;
+      d += g;
+      off += (uint64_t)g;
+      n -= (size_t)g;
+    }
+    return true;
+  };
+  bool ok = fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 12 && read_at(0, magic, 12) &&
+            memcmp(magic, "r1cs", 4) == 0;
+  if (!ok) set_error(std::string("cannot read r1cs file ") + path);
+  const uint64_t file_size = ok ? (uint64_t)sb.st_size : 0;
+  ok = ok && scan_sections(read_at, file_size, S);
+  if (ok && (!S.have[1] || !S.have[2])) { set_error("r1cs without header/constraints"); ok = false; }
+  std::vector<uint8_t> sec[6];
+  for (int t : {1, 4, 5})
+    if (ok && S.have[t]) {
+      sec[t].resize(S.size[t] + 1);  // (+ 1: a present but empty section keeps a non-null pointer)
+      if (S.size[t] && !read_at(S.off[t], sec[t].data(), S.size[t])) { set_error(std::string("cannot read r1cs file ") + path); ok = false; }
+    }
+  ok = ok && r1cs_o0_small(sec[1].data(), S.size[1], S.have[4] ? sec[4].data() : nullptr, S.size[4],
+                           S.have[5] ? sec[5].data() : nullptr, S.size[5], H);
+  if (!ok) {
+    if (fd >= 0) close(fd);
+    return false;
+  }
+  *fd_out = fd;
   return true;
 }
 
@@ -156,7 +265,7 @@ bool r1cs_gate_sections(const char *o0_r1cs, const int32_t *l2w, uint64_t n_labe
     put32(0);
   }
   std::vector<std::pair<uint32_t, std::vector<uint64_t>>> apps;
-  if (S.have[5] && !read_gate_applications(buf, S, n_labels, nullptr, &apps)) return false;
+  if (S.have[5] && !read_gate_applications(buf.data() + S.off[5], S.size[5], n_labels, nullptr, &apps)) return false;
   std::vector<uint8_t> s5;
   auto p32 = [&](uint32_t v) { s5.insert(s5.end(), (uint8_t *)&v, (uint8_t *)&v + 4); };
   auto p64 = [&](uint64_t v) { s5.insert(s5.end(), (uint8_t *)&v, (uint8_t *)&v + 8); };
@@ -241,48 +350,18 @@ int rs_read_r1cs_o0(const char *path, rs_input **out) {
   R1csSections S;
   if (!scan_sections(buf, S)) return RS_E_INVALID;
   if (!S.have[1] || !S.have[2]) { set_error("r1cs without header/constraints"); return RS_E_INVALID; }
-  Cursor hc(buf, S.off[1], S.size[1]);
-  uint32_t fs = 0;
-  if (!hc.u32(fs)) return RS_E_INVALID;
-  if (fs == 0 || fs > 32 || fs % 8) { set_error("unsupported field size"); return RS_E_INVALID; }
-  uint64_t p[4] = {0, 0, 0, 0};
-  uint32_t n_wires = 0, n_out = 0, n_pub = 0, n_prv = 0, n_cons = 0;
-  uint64_t n_labels = 0;
-  if (!hc.bytes(p, fs) || !hc.u32(n_wires) || !hc.u32(n_out) || !hc.u32(n_pub) || !hc.u32(n_prv) ||
-      !hc.u64(n_labels) || !hc.u32(n_cons))
+  R1csO0Head H;
+  if (!r1cs_o0_small(buf.data() + S.off[1], S.size[1], S.have[4] ? buf.data() + S.off[4] : nullptr, S.size[4],
+                     S.have[5] ? buf.data() + S.off[5] : nullptr, S.size[5], H))
     return RS_E_INVALID;
-  if (n_labels == 0 || n_labels > 0x7fffffffull || 1 + (uint64_t)n_out + n_pub > n_labels) {
-    set_error("r1cs header: bad label count");
-    return RS_E_INVALID;
-  }
-  // custom-gate signals (section 5, written by dag/src/r1cs_porting.rs:74-107) are forbidden:
-  // map_tree inserts every signal of a custom-gate node (dag/src/map_to_constraint_list.rs:22-24)
-  std::vector<uint32_t> gate_sigs;
-  if (S.have[5] && !read_gate_applications(buf, S, n_labels, &gate_sigs, nullptr)) return RS_E_INVALID;
-  if (S.have[4]) {  // custom gates used (r1cs_writer.rs:358-405): checked for shape only
-    Cursor gc(buf, S.off[4], S.size[4]);
-    uint32_t ng = 0;
-    if (!gc.u32(ng)) return RS_E_INVALID;
-    for (uint32_t g = 0; g < ng; ++g) {
-      uint8_t ch = 1;
-      while (ch != 0)
-        if (!gc.bytes(&ch, 1)) return RS_E_INVALID;
-      uint32_t np = 0;
-      if (!gc.u32(np) || !gc.skip((uint64_t)np * fs)) return RS_E_INVALID;
-    }
-  }
-
-  // forbidden_if_main = {0} u outputs u public inputs (dag/src/lib.rs:174, 179-204) u custom-gate
-  // signals, sorted and distinct
-  std::vector<uint32_t> forb;
-  forb.reserve(1 + (uint64_t)n_out + n_pub + gate_sigs.size());
-  for (uint64_t i = 0; i < 1 + (uint64_t)n_out + n_pub; ++i) forb.push_back((uint32_t)i);
-  forb.insert(forb.end(), gate_sigs.begin(), gate_sigs.end());
-  std::sort(forb.begin(), forb.end());
-  forb.erase(std::unique(forb.begin(), forb.end()), forb.end());
+  const uint32_t fs = H.fs, n_out = H.n_out, n_pub = H.n_pub, n_prv = H.n_prv, n_cons = H.n_cons;
+  const uint64_t n_labels = H.n_labels;
+  uint64_t p[4];
+  memcpy(p, H.prime, 32);
+  const std::vector<uint32_t> &forb = H.forbidden;
 
   Block ce, eq, lin, na, nb, nc;
-  Cursor cc(buf, S.off[2], S.size[2]);
+  Cursor cc(buf.data(), S.off[2], S.size[2]);
   std::vector<uint32_t> ks[3];
   std::vector<uint64_t> vs[3];
   for (uint32_t r = 0; r < n_cons; ++r) {
@@ -324,9 +403,7 @@ int rs_read_r1cs_o0(const char *path, rs_input **out) {
     }
   }
   rs_input *in = (rs_input *)calloc(1, sizeof(rs_input));
-  in->prime_id = RS_PRIME_CUSTOM;
-  for (int i = 0; i < 8; ++i)
-    if (memcmp(kPrimes[i], p, 32) == 0) in->prime_id = i;
+  in->prime_id = H.prime_id;
   memcpy(in->prime, p, 32);
   in->max_signal = n_labels;
   in->n_pub_out = n_out;

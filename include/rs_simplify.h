@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 9
+#define RS_ABI_VERSION 10
 
 enum rs_status {
   RS_OK = 0,
@@ -252,6 +252,13 @@ typedef struct rs_stats {
    * in its read-backs and synchronisations and replaying the largest clusters' arena order, inside the
    * span cluster_dev_ms brackets on the main stream */
   double cluster_host_ms;
+  /* ABI 10: the last rs_engine_read_r1cs_o0 -- the whole call; opening the file and streaming the
+   * constraint section to the device (until its last chunk has landed); the kernels (from there until
+   * the first D2H of the blocks is issued); the blocks' D2H into the page-locked view */
+  double read_ms;
+  double read_upload_ms;
+  double read_kernel_ms;
+  double read_d2h_ms;
 } rs_stats;
 
 typedef struct rs_engine rs_engine;
@@ -343,6 +350,19 @@ int rs_engine_inject_fault(rs_engine *eng, int where);
  * its section and the file: a truncated or malformed file is RS_E_INVALID. */
 int rs_read_r1cs_o0(const char *path, rs_input **in);
 void rs_input_free(rs_input *in);
+/* ABI 10: the same read on the device.  The result equals rs_read_r1cs_o0's field for
+ * field and array for array (rows and entries in file order, values widened to four limbs), and a file
+ * rs_read_r1cs_o0 refuses is RS_E_INVALID here too.  The host parses the section table, the header and
+ * the custom-gate sections; the constraint section goes to the device untouched (streamed through
+ * pinned staging buffers), where the linear combinations' boundaries are found in parallel and the rows
+ * classified and copied into the six blocks.  A constraint section of 16 GiB or more is RS_E_INVALID
+ * (positions are stored in 32 bits).  RS_E_NODEVICE without a gfx950 device: there is no CPU fallback.
+ * rs_engine_read_r1cs_o0: into the page-locked buffers rs_engine_flatten_dag uses (one set, shared):
+ * *in views them, valid until the next rs_engine_read_r1cs_o0 or rs_engine_flatten_dag on `eng` or
+ * rs_engine_destroy (do not rs_input_free it), and feeds rs_engine_simplify's H2D at full speed.
+ * rs_read_r1cs_o0_device: the one-shot (makes and destroys an engine); arrays freed by rs_input_free. */
+int rs_engine_read_r1cs_o0(rs_engine *eng, const char *path, const rs_input **in);
+int rs_read_r1cs_o0_device(int device, const char *path, rs_input **in);
 /* Writes the simplified .r1cs (constraint_list/src/r1cs_porting.rs:4-124). */
 int rs_write_r1cs(const char *path, const rs_input *in, const rs_output *out);
 /* The same, plus the --O0 file's custom-gate sections as the O2 writer re-emits them
@@ -401,7 +421,8 @@ int rs_flatten_dag(int device, const rs_dag *dag, rs_input **in);
 /* The same on a persistent engine (its device buffers stay allocated across calls), into page-locked
  * buffers the engine owns, so the blocks' D2H runs at PCIe speed and the result feeds
  * rs_engine_simplify's H2D at full speed too.  *in views those buffers: valid until the next
- * rs_engine_flatten_dag on `eng` or rs_engine_destroy (do not rs_input_free it). */
+ * rs_engine_flatten_dag or rs_engine_read_r1cs_o0 on `eng` or rs_engine_destroy (do not
+ * rs_input_free it). */
 int rs_engine_flatten_dag(rs_engine *eng, const rs_dag *dag, const rs_input **in);
 
 #ifdef __cplusplus

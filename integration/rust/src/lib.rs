@@ -1,10 +1,10 @@
-//! Raw bindings of `include/rs_simplify.h` (ABI 9), one item per C declaration, same order and
+//! Raw bindings of `include/rs_simplify.h` (ABI 10), one item per C declaration, same order and
 //! layout.  The safe wrapper a caller uses is `constraint_list_glue.rs` (the body that replaces
 //! `constraint_list::constraint_simplification::simplification`, constraint_simplification.rs:442).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RS_ABI_VERSION: c_int = 9;
+pub const RS_ABI_VERSION: c_int = 10;
 pub const RS_COMM_ID_BYTES: usize = 128;
 
 pub const RS_OK: c_int = 0;
@@ -218,6 +218,10 @@ pub struct rs_stats {
     pub gather_bytes: u64,
     pub gather_launches: u64,
     pub cluster_host_ms: f64,
+    pub read_ms: f64,
+    pub read_upload_ms: f64,
+    pub read_kernel_ms: f64,
+    pub read_d2h_ms: f64,
 }
 
 #[repr(C)]
@@ -256,6 +260,11 @@ extern "C" {
     pub fn rs_engine_inject_fault(eng: *mut rs_engine, where_: c_int) -> c_int;
     pub fn rs_read_r1cs_o0(path: *const c_char, inp: *mut *mut rs_input) -> c_int;
     pub fn rs_input_free(inp: *mut rs_input);
+    /// ABI 10: the same read on the device, into the engine's page-locked buffers (the view lives until
+    /// the next read or flatten on `eng`) ...
+    pub fn rs_engine_read_r1cs_o0(eng: *mut rs_engine, path: *const c_char, inp: *mut *const rs_input) -> c_int;
+    /// ... and the one-shot (arrays freed by rs_input_free).  RS_E_NODEVICE without a gfx950 device.
+    pub fn rs_read_r1cs_o0_device(device: c_int, path: *const c_char, inp: *mut *mut rs_input) -> c_int;
     pub fn rs_write_r1cs(path: *const c_char, inp: *const rs_input, out: *const rs_output) -> c_int;
     pub fn rs_write_r1cs_gates(path: *const c_char, inp: *const rs_input, out: *const rs_output, o0_r1cs: *const c_char) -> c_int;
     pub fn rs_write_sym(o0_sym: *const c_char, path: *const c_char, out: *const rs_output) -> c_int;
