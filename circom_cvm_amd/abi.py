@@ -129,7 +129,9 @@ class RsStats(C.Structure):
                 ("gather_ms", C.c_double), ("gather_bytes", C.c_uint64), ("gather_launches", C.c_uint64),
                 ("cluster_host_ms", C.c_double),
                 ("read_ms", C.c_double), ("read_upload_ms", C.c_double), ("read_kernel_ms", C.c_double),
-                ("read_d2h_ms", C.c_double)]
+                ("read_d2h_ms", C.c_double),
+                ("sym_write_ms", C.c_double), ("sym_in_ms", C.c_double), ("sym_kernel_ms", C.c_double),
+                ("sym_out_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -186,6 +188,8 @@ SYMBOLS = [
     ("rs_engine_flatten_dag", C.c_int, [C.c_void_p, C.POINTER(RsDag), C.POINTER(C.POINTER(RsInput))]),
     ("rs_engine_read_r1cs_o0", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.POINTER(RsInput))]),
     ("rs_read_r1cs_o0_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.POINTER(RsInput))]),
+    ("rs_engine_write_sym", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
+    ("rs_write_sym_device", C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.POINTER(RsOutput)]),
 ]
 
 _LIB = None
@@ -335,6 +339,12 @@ class Engine:
         check(lib().rs_engine_write_r1cs(self._h, path.encode(), o0_r1cs.encode() if o0_r1cs else None))
         return self.stats().write_ms
 
+    def write_sym(self, o0_sym: str, path: str) -> float:
+        """rs_engine_write_sym: the --O0 .sym at `o0_sym` with its witness column rewritten on the device
+        from the last result's label_to_wire.  Returns the write time (ms)."""
+        check(lib().rs_engine_write_sym(self._h, o0_sym.encode(), path.encode()))
+        return self.stats().sym_write_ms
+
     def close(self):
         if self._h:
             lib().rs_engine_destroy(self._h)
@@ -358,6 +368,12 @@ class Output:
         s = self.ptr.contents
         s._owner = self  # the struct keeps its owner (and so the library's buffers) alive
         return s
+
+    @staticmethod
+    def write_sym_device(o0_sym: str, path: str, out: RsOutput, device: int = 0):
+        """rs_write_sym_device: the one-shot device rewrite of an --O0 .sym; of `out` only n_labels and
+        label_to_wire are read."""
+        check(lib().rs_write_sym_device(device, o0_sym.encode(), path.encode(), C.byref(out)))
 
     def free(self):
         if self.ptr:

@@ -27,6 +27,7 @@
 #include <fcntl.h>
 #include <pthread.h>
 #include <sched.h>
+#include <sys/stat.h>
 #include <unistd.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -258,6 +259,7 @@ struct rs_engine {
   hipStream_t st2 = nullptr;  // the largest clusters' elimination chain runs here, beside the rest
   hipEvent_t ev[kEvCount] = {};  // (enum Ev)
   Arena A;
+  Arena SA;  // rs_engine_write_sym's buffers (sym.*): apart from A, whose generation guards the result views (fin_gen)
   bool loaded = false;
   bool have_result = false;
   int fault_at = 0;  // rs_engine_inject_fault: 1 = throw at the start of the first elimination round
@@ -703,8 +705,109 @@ static U3 excl_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, const ch
   if (x_sum) *x_sum = h[6] + h[7];
   return n ? U3{h[0] + h[3], h[1] + h[4], h[2] + h[5]} : U3{0, 0, 0};
 }
+
+// ---------------------------------------------------------------- a device image on its way to a file
+static bool pwrite_all(int fd, const uint8_t *p, uint64_t len, uint64_t off) {
+  while (len) {
+    const ssize_t w = pwrite(fd, p, len, (off_t)off);
+    if (w <= 0) return false;
+    p += w;
+    len -= (uint64_t)w;
+    off += (uint64_t)w;
+  }
+  return true;
+}
+// The way out of rs_engine_write_r1cs's and rs_engine_write_sym's images: 32 MB chunks through page-locked
+// buffers (pin slot kPinWrite) that four threads pwrite at their offsets while the next chunks' D2H run.
+// The page cache bounds it: on the GPU box's overlay file system a fresh 0.92 GB file takes 130-160 ms with
+// one or four writers (a shared mapping with four copiers: ~400 ms of page faults), the D2H ~18 ms at
+// link speed.
+struct ImageOut {
+  static constexpr uint64_t kChunk = 32ull << 20;
+  static constexpr int kBufs = 8, kThreads = 4;
+  uint8_t *pool = nullptr;
+  hipEvent_t ev[kBufs] = {};
+  ~ImageOut() {
+    for (hipEvent_t x : ev)
+      if (x) (void)hipEventDestroy(x);
+  }
+  // everything that can throw before the file exists: the pinned buffers, the events (a
+  // throw between open() and the guarded block leaked the fd or destroyed joinable threads)
+  void prepare(rs_engine *E, uint64_t bytes) {
+    const uint64_t nch = (bytes + kChunk - 1) / kChunk;
+    if (nch) pool = (uint8_t *)pin_get(E, kPinWrite, nch > 1 ? std::min<uint64_t>(nch, kBufs) * kChunk : bytes);
+    for (int b = 0; b < kBufs; ++b) HC(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
+  }
+  // src[0, bytes) (device; its producers on `st`) -> fd at img_off; a failed write sets io_err
+  void run(hipStream_t st, int fd, const uint8_t *src, uint64_t bytes, uint64_t img_off, std::atomic<bool> &io_err) {
+    const uint64_t nch = (bytes + kChunk - 1) / kChunk;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<uint64_t> work;       // chunks whose D2H is enqueued
+    std::vector<char> written(nch, 0);
+    bool closing = false;
+    // the writer threads are joined on every way out of this scope (a throw included): closing drains
+    // them, and the guard lives after everything they reference
+    struct Writers {
+      std::vector<std::thread> th;
+      std::mutex &mu;
+      std::condition_variable &cv;
+      bool &closing;
+      std::deque<uint64_t> &work;
+      void stop(bool drop) {
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          closing = true;
+          if (drop) work.clear();
+        }
+        cv.notify_all();
+        for (auto &x : th)
+          if (x.joinable()) x.join();
+      }
+      ~Writers() { stop(true); }
+    } writers{{}, mu, cv, closing, work};
+    for (int t = 0; t < kThreads && (uint64_t)t < nch; ++t)
+      writers.th.emplace_back([&]() {
+        for (;;) {
+          uint64_t i;
+          {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return closing || !work.empty(); });
+            if (work.empty()) return;
+            i = work.front();
+            work.pop_front();
+          }
+          const uint64_t off = i * kChunk, len = std::min(kChunk, bytes - off);
+          if (hipEventSynchronize(ev[i % kBufs]) != hipSuccess) io_err = true;
+          else if (!pwrite_all(fd, pool + (i % kBufs) * kChunk, len, img_off + off)) io_err = true;
+          {
+            std::lock_guard<std::mutex> lk(mu);
+            written[i] = 1;
+          }
+          cv.notify_all();
+        }
+      });
+    for (uint64_t i = 0; i < nch; ++i) {
+      if (i >= (uint64_t)kBufs) {  // the buffer's previous chunk is on disk
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return written[i - kBufs] != 0; });
+      }
+      const uint64_t off = i * kChunk, len = std::min(kChunk, bytes - off);
+      HC(hipMemcpyAsync(pool + (i % kBufs) * kChunk, src + off, len, hipMemcpyDeviceToHost, st));
+      HC(hipEventRecord(ev[i % kBufs], st));
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        work.push_back(i);
+      }
+      cv.notify_all();
+    }
+    writers.stop(false);  // every chunk written
+  }
+};
+
 #include "flatten.hpp"
 #include "r1cs_read.hpp"
+#include "sym_write.hpp"
 #include "output.hpp"
 __global__ void k_pack3(const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n, U3 *out) {
   for (uint64_t i = gtid(); i < n; i += gstride()) out[i] = U3{a[i], b[i], c[i]};
@@ -3271,10 +3374,7 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
     if (o0_r1cs && !r1cs_gate_sections(o0_r1cs, hl2w.data(), S, gates, with_gates)) return RS_E_INVALID;
     const double t_built = now_ms();
     // the file: magic + section 2's header, the device image, then sections 1 and 3 (+ the gates'
-    // sections).  The image goes out in 32 MB chunks that four threads pwrite at their offsets while
-    // the next chunks' D2H run.  The page cache bounds it: on the GPU box's overlay file system a fresh
-    // 0.92 GB file takes 130-160 ms with one or four writers (a shared mapping with four copiers:
-    // ~400 ms of page faults); the device build is 10-23 ms of it, the D2H ~18 ms at link speed
+    // sections).  The image goes out through ImageOut; the device build is 10-23 ms of the call
     std::vector<uint8_t> head, tail;
     auto put32 = [](std::vector<uint8_t> &v, uint32_t x) { const uint8_t *b = (const uint8_t *)&x; v.insert(v.end(), b, b + 4); };
     auto put64 = [](std::vector<uint8_t> &v, uint64_t x) { const uint8_t *b = (const uint8_t *)&x; v.insert(v.end(), b, b + 8); };
@@ -3300,21 +3400,8 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
       if (E->n_wires) tail.insert(tail.end(), (const uint8_t *)hw2l.data(), (const uint8_t *)(hw2l.data() + E->n_wires));
       if (with_gates) tail.insert(tail.end(), gates.begin(), gates.end());
     }
-    constexpr uint64_t kChunk = 32ull << 20;
-    constexpr int kBufs = 8, kThreads = 4;
-    const uint64_t nch = (dev_bytes + kChunk - 1) / kChunk;
-    // everything that can throw before the file exists: the pinned buffers, the events (a
-    // throw between open() and the guarded block leaked the fd or destroyed joinable threads)
-    uint8_t *pool = nch ? (uint8_t *)pin_get(E, kPinWrite, kBufs * kChunk) : nullptr;
-    struct Events {
-      hipEvent_t e[kBufs] = {};
-      ~Events() {
-        for (hipEvent_t x : e)
-          if (x) (void)hipEventDestroy(x);
-      }
-    } evs;
-    hipEvent_t *evb = evs.e;
-    for (int b = 0; b < kBufs; ++b) HC(hipEventCreateWithFlags(&evb[b], hipEventDisableTiming));
+    ImageOut io;
+    io.prepare(E, dev_bytes);
     struct Fd {
       int fd;
       ~Fd() {
@@ -3324,89 +3411,19 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
     if (file.fd < 0) throw RsError(RS_E_INVALID, std::string("cannot write ") + path);
     const int fd = file.fd;
     std::atomic<bool> io_err{false};
-    auto pwrite_all = [&](const uint8_t *p, uint64_t len, uint64_t off) {
-      while (len) {
-        const ssize_t w = pwrite(fd, p, len, (off_t)off);
-        if (w <= 0) { io_err = true; return; }
-        p += w;
-        len -= (uint64_t)w;
-        off += (uint64_t)w;
-      }
-    };
     const uint64_t img_off = head.size(), fsize = img_off + dev_bytes + tail.size();
     // the file's blocks up front (a fresh 0.92 GB file: 10.0 -> 11.4 GB/s from host memory on the GPU box's
     // /tmp, tools/writer_bench.py); a file system without fallocate gets the size by ftruncate
     if (posix_fallocate(fd, 0, (off_t)fsize) != 0 && ftruncate(fd, (off_t)fsize) != 0) io_err = true;
-    pwrite_all(head.data(), head.size(), 0);
-    pwrite_all(tail.data(), tail.size(), img_off + dev_bytes);
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<uint64_t> work;       // chunks whose D2H is enqueued
-    std::vector<char> written(nch, 0);
-    bool closing = false;
-    // the writer threads are joined on every way out of this scope (a throw included): closing drains
-    // them, and the guard lives after everything they reference
-    struct Writers {
-      std::vector<std::thread> th;
-      std::mutex &mu;
-      std::condition_variable &cv;
-      bool &closing;
-      std::deque<uint64_t> &work;
-      void stop(bool drop) {
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          closing = true;
-          if (drop) work.clear();
-        }
-        cv.notify_all();
-        for (auto &x : th)
-          if (x.joinable()) x.join();
-      }
-      ~Writers() { stop(true); }
-    } writers{{}, mu, cv, closing, work};
-    for (int t = 0; t < kThreads && (uint64_t)t < nch; ++t)
-      writers.th.emplace_back([&]() {
-        for (;;) {
-          uint64_t i;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return closing || !work.empty(); });
-            if (work.empty()) return;
-            i = work.front();
-            work.pop_front();
-          }
-          const uint64_t off = i * kChunk, len = std::min(kChunk, dev_bytes - off);
-          if (hipEventSynchronize(evb[i % kBufs]) != hipSuccess) io_err = true;
-          else pwrite_all(pool + (i % kBufs) * kChunk, len, img_off + off);
-          {
-            std::lock_guard<std::mutex> lk(mu);
-            written[i] = 1;
-          }
-          cv.notify_all();
-        }
-      });
-    const uint8_t *src = (const uint8_t *)img;
-    for (uint64_t i = 0; i < nch; ++i) {
-      if (i >= (uint64_t)kBufs) {  // the buffer's previous chunk is on disk
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return written[i - kBufs] != 0; });
-      }
-      const uint64_t off = i * kChunk, len = std::min(kChunk, dev_bytes - off);
-      HC(hipMemcpyAsync(pool + (i % kBufs) * kChunk, src + off, len, hipMemcpyDeviceToHost, st));
-      HC(hipEventRecord(evb[i % kBufs], st));
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        work.push_back(i);
-      }
-      cv.notify_all();
-    }
-    writers.stop(false);  // every chunk written
+    if (!pwrite_all(fd, head.data(), head.size(), 0)) io_err = true;
+    if (!pwrite_all(fd, tail.data(), tail.size(), img_off + dev_bytes)) io_err = true;
+    io.run(st, fd, (const uint8_t *)img, dev_bytes, img_off, io_err);
     file.fd = -1;
     if (close(fd) != 0) io_err = true;
     if (io_err) throw RsError(RS_E_INVALID, "write error");
     if (g_prof_env)
       fprintf(stderr, "[rs-prof] write_r1cs: device image %.1f MB built in %.2f ms, D2H + %d writers %.2f ms\n", dev_bytes / 1e6,
-              t_built - t0, kThreads, now_ms() - t_built);
+              t_built - t0, ImageOut::kThreads, now_ms() - t_built);
     E->stats.write_ms = now_ms() - t0;
     return RS_OK;
   } catch (const RsError &e) {
@@ -3416,6 +3433,67 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
     set_error(e.what());
     return RS_E_INTERNAL;
   }
+}
+
+// The last result's label_to_wire (resident: fin.l2w) applied to the --O0 .sym on the device
+// (sym_write.hpp): the bytes rs_write_sym writes from the fetched output.  A sharded engine: like
+// rs_engine_write_r1cs, from this rank's own complete copy, no collective.
+int rs_engine_write_sym(rs_engine *E, const char *o0_sym, const char *path) {
+  if (!E || !o0_sym || !path) { set_error("rs_engine_write_sym: null argument"); return RS_E_INVALID; }
+  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (the reader and writer threads inherit it)
+  try {
+    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
+    HC(hipSetDevice(E->device));
+    snap_join(E);  // no D2H of the result still uses the copy stream
+    const int32_t *l2w = E->A.get<int32_t>("fin.l2w", 1);
+    if (env_flag("RS_WRITER_HOST")) {  // the host writer over the fetched label_to_wire (same bytes)
+      const double t0 = now_ms();
+      std::vector<int32_t> h(E->S);
+      if (E->S) HC(hipMemcpyAsync(h.data(), l2w, 4 * E->S, hipMemcpyDeviceToHost, E->st));
+      HC(hipStreamSynchronize(E->st));
+      rs_output o{};
+      o.n_labels = E->S;
+      o.label_to_wire = h.data();
+      const int rc = rs_write_sym(o0_sym, path, &o);
+      E->stats.sym_write_ms = now_ms() - t0;
+      E->stats.sym_in_ms = E->stats.sym_kernel_ms = E->stats.sym_out_ms = 0;
+      return rc;
+    }
+    write_sym_device(E, o0_sym, path, l2w, E->S);
+    return RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    return RS_E_INTERNAL;
+  }
+}
+
+// The one-shot: out->label_to_wire goes to the device, nothing else of `out` is read.
+int rs_write_sym_device(int device, const char *o0_sym, const char *path, const rs_output *out) {
+  if (!o0_sym || !path || !out || (out->n_labels && !out->label_to_wire)) {
+    set_error("rs_write_sym_device: null argument");
+    return RS_E_INVALID;
+  }
+  rs_engine *E = nullptr;
+  int rc = rs_engine_create(device, &E);
+  if (rc) return rc;
+  try {
+    HC(hipSetDevice(E->device));
+    int32_t *l2w = E->SA.get<int32_t>("sym.l2w", out->n_labels);
+    h2d(E, l2w, out->label_to_wire, 4 * out->n_labels);
+    write_sym_device(E, o0_sym, path, l2w, out->n_labels);
+    rc = RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    rc = e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    rc = RS_E_INTERNAL;
+  }
+  rs_engine_destroy(E);
+  return rc;
 }
 
 void *rs_host_alloc(uint64_t bytes) {

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 10
+#define RS_ABI_VERSION 11
 
 enum rs_status {
   RS_OK = 0,
@@ -259,6 +259,13 @@ typedef struct rs_stats {
   double read_upload_ms;
   double read_kernel_ms;
   double read_d2h_ms;
+  /* ABI 11: the last rs_engine_write_sym -- the whole call; until the last input byte has landed on the
+   * device (the counting kernel runs under the upload, buffer by buffer); the scan, the totals' read-back
+   * and the emitting kernel; the image's D2H and the file (creating it included) */
+  double sym_write_ms;
+  double sym_in_ms;
+  double sym_kernel_ms;
+  double sym_out_ms;
 } rs_stats;
 
 typedef struct rs_engine rs_engine;
@@ -371,6 +378,34 @@ int rs_write_r1cs(const char *path, const rs_input *in, const rs_output *out);
 int rs_write_r1cs_gates(const char *path, const rs_input *in, const rs_output *out, const char *o0_r1cs);
 /* Rewrites an --O0 .sym with the witness column of `out` (constraint_list/src/sym_porting.rs). */
 int rs_write_sym(const char *o0_sym, const char *path, const rs_output *out);
+/* ABI 11: the same rewrite on the device: the engine's last result -- its label_to_wire is
+ * resident after a run -- applied to the --O0 .sym at o0_sym and written to path.  The file is streamed to
+ * the device through pinned staging buffers, column 2 of every line is replaced there by
+ * label_to_wire[column 1] (csrc/sym_write.hpp; no line table: every byte finds its place from the 23
+ * bytes before it and one prefix sum), and the image leaves through the buffers and pwrite threads of
+ * rs_engine_write_r1cs.  Positions are 64-bit; both images are resident on the device (RS_E_OOM_DEVICE if
+ * they do not fit).
+ * The accepted grammar: every non-empty line is `L,W,rest` with
+ *   L    = 0|[1-9][0-9]{0,9}   (parsed in 64 bits; L >= n_labels writes -1, as rs_write_sym does)
+ *   W    = -?[0-9]{1,10}
+ *   rest = any bytes but '\n' (may be empty, may hold commas and digits)
+ * and no byte of the file is NUL.  Empty lines are dropped, a last line without '\n' gets one, an empty
+ * file gives an empty file.  For every such file the output equals rs_write_sym's byte for byte.
+ * Anything else is RS_E_INVALID -- deliberately stricter than the host: every line rs_write_sym refuses
+ * (fewer than two commas), and the inputs on which its strtoull / %s would silently differ from a byte
+ * copy (leading zeros or blanks in L, a non-numeric L, an L of 11 or more digits, an empty or
+ * non-numeric W, a NUL).  Validation finishes before `path` is opened: a refused input leaves no
+ * output file, and the engine stays usable.
+ * RS_E_INVALID too for a null argument and for an engine without a result (like rs_engine_write_r1cs).
+ * RS_WRITER_HOST (environment) routes rs_engine_write_sym to rs_write_sym over the fetched
+ * label_to_wire, as it does for rs_engine_write_r1cs.  On a sharded engine, as rs_engine_write_r1cs:
+ * every rank holds the complete label_to_wire after a run, so any rank may call it (it is no collective)
+ * and writes the whole file.  RS_E_NODEVICE without a gfx950 device: there is no CPU fallback.
+ * Times in rs_stats.sym_*.
+ * rs_write_sym_device: the one-shot (makes and destroys an engine); of `out` it reads ONLY n_labels and
+ * label_to_wire. */
+int rs_engine_write_sym(rs_engine *eng, const char *o0_sym, const char *path);
+int rs_write_sym_device(int device, const char *o0_sym, const char *path, const rs_output *out);
 /* --json: <prefix>_constraints.json (constraint_list/src/json_porting.rs:36-48 port_constraints,
  * constraint_writers/src/json_writer.rs:4-45 ConstraintJSON): the rows in storage order with the
  * witness correspondence applied, keys ascending, decimal values. */

@@ -1,10 +1,10 @@
-//! Raw bindings of `include/rs_simplify.h` (ABI 10), one item per C declaration, same order and
+//! Raw bindings of `include/rs_simplify.h` (ABI 11), one item per C declaration, same order and
 //! layout.  The safe wrapper a caller uses is `constraint_list_glue.rs` (the body that replaces
 //! `constraint_list::constraint_simplification::simplification`, constraint_simplification.rs:442).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RS_ABI_VERSION: c_int = 10;
+pub const RS_ABI_VERSION: c_int = 11;
 pub const RS_COMM_ID_BYTES: usize = 128;
 
 pub const RS_OK: c_int = 0;
@@ -222,6 +222,10 @@ pub struct rs_stats {
     pub read_upload_ms: f64,
     pub read_kernel_ms: f64,
     pub read_d2h_ms: f64,
+    pub sym_write_ms: f64,
+    pub sym_in_ms: f64,
+    pub sym_kernel_ms: f64,
+    pub sym_out_ms: f64,
 }
 
 #[repr(C)]
@@ -268,6 +272,11 @@ extern "C" {
     pub fn rs_write_r1cs(path: *const c_char, inp: *const rs_input, out: *const rs_output) -> c_int;
     pub fn rs_write_r1cs_gates(path: *const c_char, inp: *const rs_input, out: *const rs_output, o0_r1cs: *const c_char) -> c_int;
     pub fn rs_write_sym(o0_sym: *const c_char, path: *const c_char, out: *const rs_output) -> c_int;
+    /// ABI 11: the same rewrite on the device from the engine's last result (strict `L,W,rest` grammar,
+    /// see the header; RS_E_INVALID leaves no output file) ...
+    pub fn rs_engine_write_sym(eng: *mut rs_engine, o0_sym: *const c_char, path: *const c_char) -> c_int;
+    /// ... and the one-shot, which reads only `n_labels` and `label_to_wire` of `out`.
+    pub fn rs_write_sym_device(device: c_int, o0_sym: *const c_char, path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_write_constraints_json(path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_write_substitution_json(path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_synth(kind: u32, rows: u64, seed: u64, prime_id: u32, inp: *mut *mut rs_input) -> c_int;
