@@ -639,6 +639,14 @@ static void load_abort(rs_engine *E) {
   snap_join(E);
   for (bool &pd : E->pending) pd = false;
   if (E->comm) E->comm->fail();  // the other ranks leave their collectives with an error instead of waiting
+  // A verdict can arrive in the middle of a run: the non-linear blocks' when head_overlap stages them, with
+  // the head clusters' elimination still in flight on the second stream (and the tail's on the main one).
+  // Nothing of the failed call may still be running when the next call clears and reuses the arena.
+  // (stc: above.  stx: the snapshot thread drains it before it ends, and snap_join has joined it; it is
+  // listed all the same, so that the list is every stream that touches the arena.  str: the host replay
+  // waits for its own copies, but an error thrown between two of them leaves some queued.)
+  for (hipStream_t q : {E->st, E->st2, E->ste, E->stg, E->stx, E->str})
+    if (q) (void)hipStreamSynchronize(q);
 }
 
 // A synchronous device -> host read of data whose producers the caller has already synchronised, on the

@@ -179,6 +179,7 @@ __device__ inline void d_heap_sort_pairs(uint32_t *k, Fe *v, uint32_t n) {
 }
 // Sorts every row by key and validates it (distinct keys < S, canonical nonzero values).  Skipped
 // when the block's row pointers failed k_check_ptr (`ptr_bad`, stream-ordered before this kernel).
+constexpr uint32_t kSortInsertMax = 32;  // unsorted rows up to this many entries: insertion sort; longer: heap sort
 __global__ void k_sort_validate(FieldP F, const uint64_t *ptr, uint32_t *key, Fe *val, uint64_t n,
                                 uint64_t S, const int *ptr_bad, int *err) {
   if (*ptr_bad) return;
@@ -189,7 +190,7 @@ __global__ void k_sort_validate(FieldP F, const uint64_t *ptr, uint32_t *key, Fe
     uint32_t m = (uint32_t)(e - b);
     bool sorted = true;
     for (uint32_t i = 1; i < m && sorted; ++i) sorted = k[i - 1] < k[i];
-    if (!sorted && m <= 32) {
+    if (!sorted && m <= kSortInsertMax) {
       for (uint32_t i = 1; i < m; ++i) {
         uint32_t kk = k[i];
         Fe vv = v[i];

@@ -7,6 +7,10 @@
 // the arena name of part q's buffer: pre + 'a' / 'b' / 'c' + suf
 static std::string part_name(const char *pre, int q, const char *suf) { return std::string(pre) + "abc"[q] + suf; }
 
+// Keys-first linear rows (constant_eq): at most max(kUncMin, rows / kUncDiv) rows may need their values
+// from the host input; one more and the run waits for the values and takes the frames on values.
+constexpr uint64_t kUncMin = 1024, kUncDiv = 16;
+
 // The state of one run: what simplification() (constraint_simplification.rs:442-730) keeps in its
 // locals, and one member function per phase, called in order by engine_run.  A field a phase sets for
 // a later one says so.
@@ -373,7 +377,7 @@ struct Run {
       // rows that keys alone cannot settle (a renaming collision, or no non-constant key left) take
       // their values from the host input now (hundreds of rows out of millions, typically); the rest
       // wait for their values
-      const uint64_t unc_cap = std::max<uint64_t>(1024, lin.n / 16);
+      const uint64_t unc_cap = std::max<uint64_t>(kUncMin, lin.n / kUncDiv);
       int *unc = A.get<int>("lin.unc", 1);
       uint32_t *unc_list = A.get<uint32_t>("lin.unc_list", unc_cap);
       lin_fixed = A.get<uint8_t>("lin.fixed", lin.n);
@@ -413,7 +417,7 @@ struct Run {
                (const uint32_t *)d_rows, (uint64_t)hu, lin, (const int32_t *)eq_rep, (const uint8_t *)ce_has,
                (const Fe *)ce_val, lin_fixed);
       }
-      if (g_prof_env) fprintf(stderr, "[rs-prof] keys-first: %d rows settled from host values\n", hu);
+      if (g_prof_env && keys_first) fprintf(stderr, "[rs-prof] keys-first: %d rows settled from host values\n", hu);
     }
     if (!keys_first) {
       load_wait(E, 2);

@@ -295,6 +295,10 @@ void rs_engine_destroy(rs_engine *eng);
  * until the next call on `eng` or rs_engine_destroy (do not rs_output_free it).  `in` is read
  * only during the call.  Host buffers from rs_host_alloc move at full PCIe speed; pageable ones
  * work too (HIP stages them), slower.
+ * The values of `eq` are never uploaded: values of `eq` rows the run eliminates are not inspected by
+ * rs_engine_simplify (the reference does not read them either).  A row it keeps -- both ends forbidden,
+ * a cluster of its own -- takes its values from `in` and is RS_E_INVALID when one is zero or >= p.
+ * rs_engine_load and rs_simplify validate every value of `eq`.
  */
 int rs_engine_simplify(rs_engine *eng, const rs_input *in, const rs_flags *fl, const rs_output **out);
 
