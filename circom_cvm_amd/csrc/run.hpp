@@ -1069,6 +1069,13 @@ struct Run {
     E->stats.rounds_ms += now_ms() - Tr;
     if (no_rounds > 0) no_rounds--;
     apply_round = nn > 0 && no_rounds > 0;
+    // rows that turned linear and came out empty (A and C cancelled) are still the reference's next
+    // list (:380-394 take linear_id as it is), so its loop makes one more round, over nothing.  Nothing
+    // to run here, but the round counts -- as round 2 does after a first round that left only such rows
+    if (nn == 0 && !turned.empty() && no_rounds > 0) {
+      E->stats.rounds++;
+      no_rounds--;
+    }
   }
   // ordered substitutions of the round: cluster order, ascending `from` -- one sort of the
   // (cluster, from) keys of the valid slots on the device; the host fetches the list only when

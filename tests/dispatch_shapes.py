@@ -281,6 +281,34 @@ def merge_pair(b: Builder, glue: int, len_a: int, len_b: int):
     b.lin([z, glue] + b.forbid(len_b - 2))
 
 
+def cancel_pair(b: Builder, glue: int, length: int, kind: str) -> dict:
+    """Two rows of length + 1 entries -- the forbidden `glue`, length - 2 fresh forbidden signals, a
+    constant and their only takeable signal z, which they share -- the second the first times a
+    non-unit coefficient.  Whichever is popped first becomes z's holder with `length` right-hand-side
+    terms; the other conflicts with it and every term of the merge cancels:
+      "empty"    the merged row is 0 = 0 and is dropped;
+      "const"    the second row's constant is changed: the merge leaves 0 = c, c != 0, a leftover row;
+      "partial"  one fresh forbidden coefficient of the second row is changed: the other length - 1
+                 terms cancel and that key survives alone, a leftover row without a takeable signal."""
+    assert length >= 4 and kind in ("empty", "const", "partial")
+    p = b.p
+    z = b.take(1)[0]
+    f = b.forbid(length - 2)
+    first = {0: b.coef(), z: b.coef(), glue: b.coef()}
+    first.update({s: b.coef() for s in f})
+    kk = b.rng.randrange(2, p - 1)
+    second = {s: v * kk % p for s, v in first.items()}
+    if kind != "empty":
+        at = 0 if kind == "const" else f[len(f) // 2]
+        second[at] = (second[at] + 1) % p or 1
+        assert second[at] != first[at] * kk % p
+    for m in (first, second):
+        assert all(m.values())
+        b.rows.append(R.Con({}, {}, m))
+        b.n_lin += 1
+    return dict(z=z, work_plus_rhs=2 * length + 1, survivor=None if kind != "partial" else f[len(f) // 2])
+
+
 def star(b: Builder, length: int) -> int:
     """x + c_0 + sum_{k < length-1} c_k f_k = 0 with every f forbidden: the substitution of x has
     exactly `length` right-hand-side terms.  Returns x."""
@@ -290,9 +318,28 @@ def star(b: Builder, length: int) -> int:
     return x
 
 
+def twin_stars(b: Builder, length: int):
+    """Two stars over the same length - 1 forbidden signals and constant whose right-hand sides are
+    proportional: x1 = r1 * E and x2 = r2 * E for one expression E of `length` terms.  Returns
+    (x1, x2, ratio): a * x1 + (a * ratio) * x2 substitutes to `length` explicit zeros, for any a."""
+    assert length >= 3
+    p = b.p
+    x1, x2 = b.take(2)
+    f = b.forbid(length - 1)
+    e = {0: b.coef()}
+    e.update({s: b.coef() for s in f})
+    v1, v2, kk = b.coef(), b.coef(), b.rng.randrange(2, p - 1)
+    b.rows.append(R.Con({}, {}, {**e, x1: v1}))
+    b.rows.append(R.Con({}, {}, {**{s: v * kk % p for s, v in e.items()}, x2: v2}))
+    b.n_lin += 2
+    # x1 = -E / v1, x2 = -kk E / v2: a / v1 + a ratio kk / v2 = 0
+    return x1, x2, (p - 1) * v2 % p * pow(v1 * kk % p, -1, p) % p
+
+
 def quad(b: Builder, spec_a, spec_b, spec_c) -> int:
     """One non-linear row.  Each spec lists the entries of A, B, C: "p" a plain signal nothing
-    substitutes, "c" the constant, an int L a signal substituted by a star of L terms."""
+    substitutes, "c" the constant, an int L a signal substituted by a star of L terms, ("twin", L)
+    both signals of twin_stars(L) with coefficients under which their 2 L terms cancel."""
     def lc(spec):
         m = {}
         for e in spec:
@@ -300,6 +347,11 @@ def quad(b: Builder, spec_a, spec_b, spec_c) -> int:
                 m[0] = b.coef()
             elif e == "p":
                 m[b.forbid(1)[0]] = b.coef()
+            elif isinstance(e, tuple):
+                assert e[0] == "twin"
+                x1, x2, ratio = twin_stars(b, e[1])
+                m[x1] = b.coef()
+                m[x2] = m[x1] * ratio % b.p
             else:
                 m[star(b, int(e))] = b.coef()
         return m
@@ -319,26 +371,62 @@ def late_star(b: Builder, length: int) -> int:
     return x
 
 
-def storage_row(b: Builder, n_plain: int, late_lengths) -> int:
+def late_twins(b: Builder, length: int):
+    """twin_stars for round 2: two late_star rows whose linear forms are proportional but for their
+    own signals x1, x2.  Returns (x1, x2, ratio) as twin_stars does."""
+    assert length >= 3
+    p = b.p
+    x1, x2 = b.take(2)
+    f = b.forbid(length - 1)
+    c = {s: b.coef() for s in f[1:]}
+    c[0] = b.coef()
+    s1, s2, bx1, bx2, bf, kk = b.coef(), b.coef(), b.coef(), b.coef(), b.coef(), b.rng.randrange(2, p - 1)
+    # C - s B: E - s1 bx1 x1 and kk E - s2 bx2 x2 with E = C - s1 bf f0
+    b.nonlin({0: s1}, {x1: bx1, f[0]: bf}, dict(c))
+    b.nonlin({0: s2}, {x2: bx2, f[0]: kk * s1 % p * bf % p * pow(s2, -1, p) % p}, {q: v * kk % p for q, v in c.items()})
+    return x1, x2, (p - 1) * s2 % p * bx2 % p * pow(s1 * bx1 % p * kk % p, -1, p) % p
+
+
+def storage_row(b: Builder, n_plain: int, late_lengths, twin_a=None, twin_c=None) -> int:
     """A non-linear row round 1 leaves as it is (A and B one plain signal each): C holds n_plain plain
-    signals and one signal per entry of late_lengths that round 2 substitutes by that many terms."""
+    signals and one signal per entry of late_lengths that round 2 substitutes by that many terms.
+    twin_a / twin_c = L: A is (C also holds) the two signals of late_twins(L) with coefficients under
+    which round 2's substitutions cancel -- round 1 still leaves the row alone."""
     c = {b.forbid(1)[0]: b.coef() for _ in range(n_plain)}
     for ln in late_lengths:
         c[late_star(b, ln)] = b.coef()
-    return b.nonlin({b.forbid(1)[0]: b.coef()}, {b.forbid(1)[0]: b.coef()}, c)
+    a = {b.forbid(1)[0]: b.coef()} if twin_a is None else {}
+    for m, ln in ((a, twin_a), (c, twin_c)):
+        if ln is not None:
+            x1, x2, ratio = late_twins(b, ln)
+            m[x1] = b.coef()
+            m[x2] = m[x1] * ratio % b.p
+    return b.nonlin(a, {b.forbid(1)[0]: b.coef()}, c)
 
 
-def dep_sub(b: Builder, n_own: int, n_dep: int, dep_len: int, pad: int) -> dict:
+def dep_sub(b: Builder, n_own: int, n_dep: int, dep_len: int, pad: int, cancel: int = 0, inherit: bool = False) -> dict:
     """A process_3 cluster whose normalised substitution for one signal s has n_own entries that no
     substitution holds (the constant slot and n_own - 1 forbidden signals) and n_dep entries that are
     themselves holders, each with dep_len right-hand-side terms.  `pad` more rows (sharing a
-    forbidden signal of s's row) bring the cluster into the workgroup class."""
+    forbidden signal of s's row) bring the cluster into the workgroup class.
+    cancel = m: the first 2 m dependencies pair up, each pair over one shared forbidden signal q (in
+    place of a fresh one: dep_len stays), and s's coefficient of the pair's second holder is solved so
+    that q cancels in the composed right-hand side of s: m explicit zero keys, which the reference
+    keeps.  inherit: one more holder t above s whose row contains s, so its composed right-hand
+    side carries the zero keys of s.  The defaults consume nothing and give the plain rows."""
     assert n_own >= 2 and dep_len >= 2
+    assert 2 * cancel <= n_dep and (cancel == 0 or dep_len >= 3)
+    p = b.p
     h = b.take(n_dep)
     s = b.take(1)[0]           # above every h: take_signal_3 picks it in its own row
+    t = b.take(1)[0] if inherit else None   # above s
     g = b.forbid(n_own - 1)
+    q = b.forbid(cancel)
     first = b.n_lin
     for j in range(n_dep):
+        if j < 2 * cancel:
+            b.lin([h[j], q[j // 2]] + b.forbid(dep_len - 2))
+            continue
         f = b.forbid(dep_len - 1)
         if dep_len == 2:        # two signals: keep it from being an equality
             b.rows.append(R.Con({}, {}, {h[j]: 1, f[0]: 2 + j}))
@@ -349,10 +437,44 @@ def dep_sub(b: Builder, n_own: int, n_dep: int, dep_len: int, pad: int) -> dict:
     if len(keys) < 3:
         keys += b.forbid(3 - len(keys))
     b.lin(keys)
+    row_s = b.rows[-1].c
+    for i in range(cancel):
+        # h = -(b q + ..) / c per holder row: a1 b1 / c1 + a2 b2 / c2 = 0 cancels q in s
+        r1, r2 = b.rows[-1 - n_dep + 2 * i].c, b.rows[-n_dep + 2 * i].c
+        h1, h2 = h[2 * i], h[2 * i + 1]
+        row_s[h2] = (p - 1) * row_s[h1] % p * r1[q[i]] % p * r2[h2] % p * pow(r1[h1] * r2[q[i]] % p, -1, p) % p
+        assert row_s[h2] != 0
     ys = b.take(pad)
     for yv in ys:
         b.lin([yv, g[0]] + b.forbid(1))
-    return dict(s=s, first=first, n=n_dep + 1 + pad, probe=[s] + h[:4] + ys[:4])
+    if inherit:
+        b.lin([t, s] + b.forbid(1))
+    return dict(s=s, t=t, zeros=q, first=first, n=n_dep + 1 + pad + int(inherit), probe=[s] + h[:4] + ys[:4] + ([t] if inherit else []))
+
+
+def zero_sub(b: Builder, dep_len: int, pad: int) -> dict:
+    """A process_3 cluster in which every non-constant key of one substitution cancels: two holders
+    h1, h2 over the same dep_len - 1 forbidden signals with proportional rows, and s + a1 h1 + a2 h2
+    = 0 with a1, a2 solved as in dep_sub(cancel=..): the composed right-hand side of s is the
+    constant slot and dep_len - 1 explicit zeros.  t's row holds s and inherits them; `pad` more
+    rows share a forbidden signal of the holders' rows."""
+    assert dep_len >= 3
+    p = b.p
+    h1, h2, s, t = b.take(4)
+    f = b.forbid(dep_len - 1)
+    first = b.n_lin
+    e = {q: b.coef() for q in f}
+    c1, c2, kk, a1 = b.coef(), b.coef(), b.rng.randrange(2, p - 1), b.coef()
+    a2 = (p - 1) * a1 % p * c2 % p * pow(c1 * kk % p, -1, p) % p
+    for m in ({**e, h1: c1}, {**{q: v * kk % p for q, v in e.items()}, h2: c2}, {s: b.coef(), h1: a1, h2: a2}):
+        assert all(m.values())
+        b.rows.append(R.Con({}, {}, m))
+        b.n_lin += 1
+    ys = b.take(pad)
+    for yv in ys:
+        b.lin([yv, f[0]] + b.forbid(1))
+    b.lin([t, s] + b.forbid(1))
+    return dict(s=s, t=t, zeros=f, first=first, n=4 + pad, probe=[s, t, h1, h2] + ys[:4])
 
 
 # ============================================================================ certificates
@@ -447,11 +569,22 @@ def cluster_rows(sys_: "R.System", shape: dict) -> List["R.Con"]:
     return cl[0]
 
 
+def merge_kind(work: "R.Con", forbidden) -> str:
+    """What a conflict merge left: "empty" (0 = 0, dropped), "const" (only key 0, non-zero: 0 = c, a
+    leftover row), "forbidden" (no takeable signal left: a leftover row) or "live" (the loop goes on)."""
+    if R.is_empty(work):
+        return "empty"
+    if set(work.c) == {0}:
+        return "const"
+    return "forbidden" if R.take_signal_3(forbidden, work) is None else "live"
+
+
 def elimination_trace(cluster: List["R.Con"], forbidden, p: int, p4: bool):
     """substitution_process_3 / _4 step by step with pyref's own pieces, recording what the ordered
     loops branch on: the length of every row as it is popped and, per conflict, (work length,
-    holder right-hand-side length).  The holder it ends with is checked against pyref's."""
-    pops, merges = [], []
+    holder right-hand-side length) in `merges` and (work length, right-hand-side length, length of
+    the merged row, merge_kind of it) in `results`.  The holder it ends with is checked against pyref's."""
+    pops, merges, results = [], [], []
     holder: dict = {}
     if not p4:
         cons = list(cluster)
@@ -468,6 +601,7 @@ def elimination_trace(cluster: List["R.Con"], forbidden, p: int, p4: bool):
                     break
                 merges.append((len(work.c), len(holder[out][1])))
                 work = R.merge_conflict(coef, to, holder[out][0], holder[out][1], p)
+                results.append(merges[-1] + (len(work.c), merge_kind(work, forbidden)))
         ref: dict = {}
         R.substitution_process_3(forbidden, cluster, ref, p)
     else:
@@ -511,18 +645,31 @@ def elimination_trace(cluster: List["R.Con"], forbidden, p: int, p4: bool):
                     break
                 merges.append((len(work.c), len(holder[out][1])))
                 work = R.merge_conflict(coef, to, holder[out][0], holder[out][1], p)
+                results.append(merges[-1] + (len(work.c), merge_kind(work, forbidden)))
         ref = {}
         R.substitution_process_4(forbidden, cluster, ref, p)
     assert holder == ref, "the trace diverged from pyref"
-    return dict(pops=pops, merges=merges, holder=holder)
+    return dict(pops=pops, merges=merges, results=results, holder=holder)
 
 
-def compose_shape(sys_: "R.System", shape: dict, s: int) -> dict:
+def compose_shape(sys_: "R.System", shape: dict, s: int, p4: bool = False) -> dict:
     """For the process_3 substitution of s, before composition: its length, how many of its entries
     are holders, and E = own entries + the (composed) lengths of those holders' right-hand sides --
-    what d_compose_wave / d_compose_merge compare (kernels.hpp)."""
+    what d_compose_wave / d_compose_merge compare (kernels.hpp).  p4: the same for a process_4
+    cluster, composed in its deletion order (create_nonoverlapping_substitutions_4); every holder
+    among s's entries must then be final before s."""
     cl = cluster_rows(sys_, shape)
     holder: dict = {}
+    if p4:
+        _, order = R.substitution_process_4(sys_.forbidden, cl, holder, sys_.p)
+        norm = R.normalize_substitutions(holder, sys_.p)
+        pre = dict(norm[s].to)
+        final = R.create_nonoverlapping_substitutions_4(copy.deepcopy(norm), order, sys_.p)
+        deps = [q for q in pre if q in holder]
+        assert all(order.index(q) < order.index(s) for q in deps)
+        n_own = len(pre) - len(deps)
+        tot = sum(len(final[q].to) for q in deps)
+        return dict(length=len(pre), holders=len(deps), own=n_own, dep_total=tot, E=n_own + tot)
     R.substitution_process_3(sys_.forbidden, cl, holder, sys_.p)
     norm = R.normalize_substitutions(holder, sys_.p)
     pre = dict(norm[s].to)
@@ -606,6 +753,41 @@ def linear_rounds(sys_: "R.System", rounds, old=False) -> int:
     finally:
         R.linear_simplification = real
     return n[0]
+
+
+def log_diff(got, ref) -> Optional[str]:
+    """None when two logs [(from, {signal: value})] are equal entry for entry -- `from`, the keys, the
+    values (zeros included) and the order --, else the first difference."""
+    if len(got) != len(ref):
+        return f"{len(got)} entries vs {len(ref)}"
+    for i, (x, y) in enumerate(zip(got, ref)):
+        if x != y:
+            return f"entry {i}: {x} vs {y}"
+    return None
+
+
+def zero_keys(to: dict) -> List[int]:
+    """The zero-valued non-constant keys of a right-hand side (the constant slot is 0 in every
+    substitution without a constant term, so it tells nothing)."""
+    return sorted(s for s, v in to.items() if s != 0 and v == 0)
+
+
+def zero_entries(log) -> List[int]:
+    """The positions of the log entries that hold a zero-valued non-constant key."""
+    return [i for i, (_, to) in enumerate(log) if zero_keys(to)]
+
+
+def pruned(log):
+    """The log an implementation that dropped zero-valued non-constant keys would write."""
+    return [(frm, {s: v for s, v in to.items() if s == 0 or v != 0}) for frm, to in log]
+
+
+def log_family(name: str) -> str:
+    """The family of a case of CASES, by the part of the table that makes it."""
+    for pre in ("row", "merge", "compose", "giant", "round2", "frames"):
+        if name.startswith(pre + "_"):
+            return pre
+    return "cluster"
 
 
 # ============================================================================ the cases

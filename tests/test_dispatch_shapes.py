@@ -110,6 +110,51 @@ def test_case_table_is_complete():
             assert c.n_rounds is not None
 
 
+# ---------------------------------------------------------------------------- the log's reference
+_LOGS = {}
+
+
+def _log_licence(case):
+    """(difference between refcpu's log and pyref's literal log, entries with a zero-valued
+    non-constant key) of a case at its first variant -- the run tests/test_gpu_dispatch_log.py makes."""
+    if case.name not in _LOGS:
+        prime, old, rounds = ds.variants(case)[0]
+        sys_, _ = case.build(R.PRIMES[prime])
+        h = rsio.InputHolder(sys_)
+        fl = rsio.flags("O2", rounds, old, log=True)
+        ref = rsio.pyref_log(R.simplification(sys_, rsio.py_flags(fl), want_log=True).log)
+        got = rsio.oracle_run_log(h.inp, fl, threads=8)[3]
+        _LOGS[case.name] = (ds.log_diff(got, ref), len(ds.zero_entries(ref)), len(ref))
+    return _LOGS[case.name]
+
+
+@pytest.mark.parametrize("case", ds.CASES, ids=[c.name for c in ds.CASES])
+def test_refcpu_log_is_pyrefs(case):
+    """refcpu's substitution log equals pyref's literal one (zero-valued keys kept), entry for entry:
+    what makes refcpu the reference of tests/test_gpu_dispatch_log.py.  No case is left out."""
+    d, _, _ = _log_licence(case)
+    assert d is None, f"refcpu's log differs from pyref's: {d}"
+
+
+def test_every_family_logs_a_zero_key():
+    """At least one log of each family holds a zero-valued non-constant key, so comparing the logs of
+    the existing cases already tells a pool that keeps explicit zeros from one that prunes them.
+    The round2_* cases cannot hold one whatever their seeds: round 2 meets each late star as a cluster
+    of one row, and a zero key needs a composition.  For that family the log counted with theirs is the
+    certified round-2 composition of cancel_cases.py (zero_round2), which the GPU runs with the log on
+    like the rest."""
+    import cancel_cases as cc
+    have = {}
+    for case in ds.CASES + [c for c in cc.CANCEL_CASES if c.name == "zero_round2"]:
+        d, zeros, _ = _log_licence(case)
+        assert d is None, f"{case.name}: {d}"
+        fam = "round2" if case.name == "zero_round2" else ds.log_family(case.name)
+        have[fam] = have.get(fam, 0) + (zeros > 0)
+    assert set(have) == {"cluster", "row", "merge", "compose", "giant", "round2", "frames"}
+    for fam in ("cluster", "row", "merge", "compose", "giant", "round2"):
+        assert have[fam] >= 1, f"no log of the {fam} cases holds a zero-valued non-constant key"
+
+
 # ---------------------------------------------------------------------------- the build's dependency list
 def _includes(path):
     with open(path) as f:
