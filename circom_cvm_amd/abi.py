@@ -137,6 +137,15 @@ class RsStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RsJsonStats(C.Structure):
+    """rs_json_stats: the last rs_engine_write_constraints_json / rs_engine_write_substitution_json."""
+    _fields_ = [("write_ms", C.c_double), ("in_ms", C.c_double), ("kernel_ms", C.c_double),
+                ("out_ms", C.c_double), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RsDag(C.Structure):
     """rs_dag: the component DAG rs_flatten_dag expands."""
     _fields_ = [("prime_id", C.c_uint32), ("prime", C.c_uint64 * 4),
@@ -190,6 +199,11 @@ SYMBOLS = [
     ("rs_read_r1cs_o0_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(C.POINTER(RsInput))]),
     ("rs_engine_write_sym", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
     ("rs_write_sym_device", C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.POINTER(RsOutput)]),
+    ("rs_engine_write_constraints_json", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rs_engine_write_substitution_json", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rs_write_constraints_json_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(RsOutput)]),
+    ("rs_write_substitution_json_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(RsOutput)]),
+    ("rs_engine_json_stats", C.c_int, [C.c_void_p, C.POINTER(RsJsonStats)]),
 ]
 
 _LIB = None
@@ -345,6 +359,23 @@ class Engine:
         check(lib().rs_engine_write_sym(self._h, o0_sym.encode(), path.encode()))
         return self.stats().sym_write_ms
 
+    def write_constraints_json(self, path: str) -> float:
+        """rs_engine_write_constraints_json: the last result as <prefix>_constraints.json, formatted on the
+        device.  Returns the write time (ms)."""
+        check(lib().rs_engine_write_constraints_json(self._h, path.encode()))
+        return self.json_stats().write_ms
+
+    def write_substitution_json(self, path: str) -> float:
+        """rs_engine_write_substitution_json: the last run's substitution log as
+        <prefix>_substitutions.json, formatted on the device.  Returns the write time (ms)."""
+        check(lib().rs_engine_write_substitution_json(self._h, path.encode()))
+        return self.json_stats().write_ms
+
+    def json_stats(self) -> RsJsonStats:
+        s = RsJsonStats()
+        check(lib().rs_engine_json_stats(self._h, C.byref(s)))
+        return s
+
     def close(self):
         if self._h:
             lib().rs_engine_destroy(self._h)
@@ -374,6 +405,17 @@ class Output:
         """rs_write_sym_device: the one-shot device rewrite of an --O0 .sym; of `out` only n_labels and
         label_to_wire are read."""
         check(lib().rs_write_sym_device(device, o0_sym.encode(), path.encode(), C.byref(out)))
+
+    @staticmethod
+    def write_constraints_json_device(path: str, out: RsOutput, device: int = 0):
+        """rs_write_constraints_json_device: the one-shot device writer of <prefix>_constraints.json."""
+        check(lib().rs_write_constraints_json_device(device, path.encode(), C.byref(out)))
+
+    @staticmethod
+    def write_substitution_json_device(path: str, out: RsOutput, device: int = 0):
+        """rs_write_substitution_json_device: the one-shot device writer of <prefix>_substitutions.json; of
+        `out` only n_log, log_from and log_to are read."""
+        check(lib().rs_write_substitution_json_device(device, path.encode(), C.byref(out)))
 
     def free(self):
         if self.ptr:

@@ -14,7 +14,11 @@
 // same engine (rs_engine_simplify); --host-reader reads it with rs_read_r1cs_o0 and runs the one-shot
 // rs_simplify instead.  On the engine path the .sym is rewritten on the device too (rs_engine_write_sym,
 // from the label_to_wire the run left there; it accepts the `L,W,rest` lines circom writes, see the
-// header); --host-reader keeps rs_write_sym.  The files and the summary are the same bytes either way.
+// header); --host-reader keeps rs_write_sym.  The --json and --simplification_substitution files are
+// formatted on the device as well on the engine path (rs_engine_write_constraints_json,
+// rs_engine_write_substitution_json, from the result and the log the run left with the engine);
+// --host-reader keeps rs_write_constraints_json / rs_write_substitution_json.  The files and the summary
+// are the same bytes either way.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -80,8 +84,8 @@ int main(int argc, char **argv) {
   }
   if (rs_write_r1cs_gates((out + ".r1cs").c_str(), in, o, in_r1cs)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
   if (in_sym && (eng ? rs_engine_write_sym(eng, in_sym, (out + ".sym").c_str()) : rs_write_sym(in_sym, (out + ".sym").c_str(), o))) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
-  if (json && rs_write_constraints_json((out + "_constraints.json").c_str(), o)) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
-  if (fl.emit_substitution_log && rs_write_substitution_json((out + "_substitutions.json").c_str(), o)) {
+  if (json && (eng ? rs_engine_write_constraints_json(eng, (out + "_constraints.json").c_str()) : rs_write_constraints_json((out + "_constraints.json").c_str(), o))) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
+  if (fl.emit_substitution_log && (eng ? rs_engine_write_substitution_json(eng, (out + "_substitutions.json").c_str()) : rs_write_substitution_json((out + "_substitutions.json").c_str(), o))) {
     fprintf(stderr, "error: %s\n", rs_last_error());
     return 1;
   }

@@ -259,7 +259,7 @@ struct rs_engine {
   hipStream_t st2 = nullptr;  // the largest clusters' elimination chain runs here, beside the rest
   hipEvent_t ev[kEvCount] = {};  // (enum Ev)
   Arena A;
-  Arena SA;  // rs_engine_write_sym's buffers (sym.*): apart from A, whose generation guards the result views (fin_gen)
+  Arena SA;  // rs_engine_write_sym's and the JSON writers' buffers (sym.*, json.*): apart from A, whose generation guards the result views (fin_gen)
   bool loaded = false;
   bool have_result = false;
   int fault_at = 0;  // rs_engine_inject_fault: 1 = throw at the start of the first elimination round
@@ -280,6 +280,7 @@ struct rs_engine {
   uint64_t out_nnz[3] = {0, 0, 0};
   uint64_t n_wires = 0, npiw = 0;
   rs_stats stats{};
+  rs_json_stats jstats{};  // the last JSON writer call of either kind
   // sharded elimination: this engine is rank `comm->rank` of `comm->world`
   std::unique_ptr<rs::Comm> comm;
   // substitution log of the last run (rs_flags.emit_substitution_log), canonical values
@@ -816,6 +817,7 @@ struct ImageOut {
 #include "flatten.hpp"
 #include "r1cs_read.hpp"
 #include "sym_write.hpp"
+#include "json_write.hpp"
 #include "output.hpp"
 __global__ void k_pack3(const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n, U3 *out) {
   for (uint64_t i = gtid(); i < n; i += gstride()) out[i] = U3{a[i], b[i], c[i]};
@@ -3492,6 +3494,205 @@ int rs_write_sym_device(int device, const char *o0_sym, const char *path, const 
     int32_t *l2w = E->SA.get<int32_t>("sym.l2w", out->n_labels);
     h2d(E, l2w, out->label_to_wire, 4 * out->n_labels);
     write_sym_device(E, o0_sym, path, l2w, out->n_labels);
+    rc = RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    rc = e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    rc = RS_E_INTERNAL;
+  }
+  rs_engine_destroy(E);
+  return rc;
+}
+
+// ---- the --json and --simplification_substitution files on the device (json_write.hpp)
+namespace rs {
+// RS_WRITER_HOST: the host writer over the fetched result (same bytes); bytes: the file less `framing`
+static int json_via_host(rs_engine *E, const char *path, bool log) {
+  const double t0 = now_ms();
+  rs_output *o = nullptr;
+  int rc = rs_engine_fetch(E, &o);
+  if (rc != RS_OK) return rc;
+  rc = log ? rs_write_substitution_json(path, o) : rs_write_constraints_json(path, o);
+  rs_output_free(o);
+  struct stat sb;
+  const uint64_t framing = log ? 3 : 22;
+  E->jstats = rs_json_stats{};
+  E->jstats.write_ms = now_ms() - t0;
+  if (rc == RS_OK && stat(path, &sb) == 0 && (uint64_t)sb.st_size >= framing) E->jstats.bytes = (uint64_t)sb.st_size - framing;
+  return rc;
+}
+}  // namespace rs
+
+// The last result's constraints (resident: the compact CSR, fin.l2w) as <prefix>_constraints.json.  A
+// sharded engine: like rs_engine_write_r1cs, from this rank's own complete copy, no collective.
+int rs_engine_write_constraints_json(rs_engine *E, const char *path) {
+  if (!E || !path) { set_error("rs_engine_write_constraints_json: null argument"); return RS_E_INVALID; }
+  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (the writer threads inherit it)
+  try {
+    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
+    HC(hipSetDevice(E->device));
+    snap_join(E);  // no D2H of the result still uses the copy stream
+    if (env_flag("RS_WRITER_HOST")) return json_via_host(E, path, false);
+    const double t0 = now_ms();
+    ensure_csr(E);  // (before the writer's own buffers: they live in another arena and move nothing of the result)
+    const char *nm[3] = {"out.a", "out.b", "out.c"};
+    JsonSrc s;
+    s.n = E->out_n_dev;
+    s.nparts = 3;
+    for (int q = 0; q < 3; ++q) {
+      s.ptr[q] = E->A.get<uint64_t>(std::string(nm[q]) + ".ptr", 1);
+      s.col[q] = E->A.get<uint32_t>(std::string(nm[q]) + ".col", 1);
+      s.val[q] = E->A.get<uint64_t>(std::string(nm[q]) + ".val", 1);
+      s.nnz[q] = E->out_nnz[q];
+    }
+    s.l2w = E->A.get<int32_t>("fin.l2w", 1);
+    s.n_labels = E->S;
+    write_json_device(E, s, path, t0, t0);
+    return RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    return RS_E_INTERNAL;
+  }
+}
+
+// The last run's substitution log (the engine's host vectors) as <prefix>_substitutions.json: up through
+// the pinned staging pool on the copy stream, then the formatter.
+int rs_engine_write_substitution_json(rs_engine *E, const char *path) {
+  if (!E || !path) { set_error("rs_engine_write_substitution_json: null argument"); return RS_E_INVALID; }
+  CpuNear cpu_near_(E);
+  try {
+    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
+    HC(hipSetDevice(E->device));
+    snap_join(E);
+    if (env_flag("RS_WRITER_HOST")) return json_via_host(E, path, true);
+    const double t0 = now_ms();
+    JsonSrc s;
+    s.nparts = 1;
+    s.n = E->log_on ? E->log_from.size() : 0;
+    double t_in = t0;
+    if (s.n) {
+      const uint64_t n = s.n, nnz = E->log_key.size();
+      if (E->log_ptr.size() != n + 1 || E->log_ptr[n] != nnz || E->log_val.size() != 4 * nnz)
+        throw RsError(RS_E_INTERNAL, "the substitution log's arrays disagree");
+      Arena &A = E->SA;
+      uint32_t *from = A.get<uint32_t>("json.log.from", n), *key = A.get<uint32_t>("json.log.key", nnz);
+      uint64_t *ptr = A.get<uint64_t>("json.log.ptr", n + 1), *val = A.get<uint64_t>("json.log.val", 4 * nnz);
+      const uint64_t all = 4 * n + 8 * (n + 1) + 36 * nnz;
+      const uint64_t stage = std::min<uint64_t>(kRrStage, (all + 4095) & ~4095ull);
+      uint8_t *pool = (uint8_t *)pin_get(E, kPinStage, kRrBufs * stage);
+      struct Events {
+        hipEvent_t e[kRrBufs] = {};
+        ~Events() {
+          for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+        }
+      } evs;
+      for (hipEvent_t &x : evs.e) HC(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+      struct Drain {  // the pool is free again on every way out
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+      } drain{E->stc};
+      uint64_t seq = 0;
+      json_stage_up(E, pool, stage, evs.e, seq, from, E->log_from.data(), 4 * n);
+      json_stage_up(E, pool, stage, evs.e, seq, ptr, E->log_ptr.data(), 8 * (n + 1));
+      json_stage_up(E, pool, stage, evs.e, seq, key, E->log_key.data(), 4 * nnz);
+      json_stage_up(E, pool, stage, evs.e, seq, val, E->log_val.data(), 32 * nnz);
+      HC(hipStreamSynchronize(E->stc));
+      t_in = now_ms();
+      s.from = from;
+      s.ptr[0] = ptr;
+      s.col[0] = key;
+      s.val[0] = val;
+      s.nnz[0] = nnz;
+    }
+    write_json_device(E, s, path, t0, t_in);
+    return RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    return RS_E_INTERNAL;
+  }
+}
+
+int rs_engine_json_stats(rs_engine *E, rs_json_stats *st) {
+  if (!E || !st) { set_error("rs_engine_json_stats: null argument"); return RS_E_INVALID; }
+  *st = E->jstats;
+  return RS_OK;
+}
+
+// The one-shots: what they read of `out` goes to the device (rows in ABI 8's streamed layout, or CSR rows
+// that do not start at 0, are compacted on the host first).
+int rs_write_constraints_json_device(int device, const char *path, const rs_output *out) {
+  if (!path || !out || (out->n_labels && !out->label_to_wire)) {
+    set_error("rs_write_constraints_json_device: null argument");
+    return RS_E_INVALID;
+  }
+  rs_engine *E = nullptr;
+  int rc = rs_engine_create(device, &E);
+  if (rc) return rc;
+  try {
+    HC(hipSetDevice(E->device));
+    const double t0 = now_ms();
+    const rs_lc *L[3] = {&out->a, &out->b, &out->c};
+    const uint32_t *len[3] = {out->a_len, out->b_len, out->c_len};
+    const char *nm[3] = {"json.in.a", "json.in.b", "json.in.c"};
+    JsonHostPart hp[3];
+    JsonSrc s;
+    s.n = out->n_constraints;
+    s.nparts = 3;
+    for (int q = 0; q < 3; ++q) {
+      json_host_part(out, q, *L[q], s.n, len[q], hp[q]);
+      json_upload_part(E, hp[q], s.n, nm[q], q, s);
+    }
+    int32_t *l2w = E->SA.get<int32_t>("json.in.l2w", out->n_labels);
+    if (out->n_labels) HC(hipMemcpyAsync(l2w, out->label_to_wire, 4 * out->n_labels, hipMemcpyHostToDevice, E->st));
+    HC(hipStreamSynchronize(E->st));
+    s.l2w = l2w;
+    s.n_labels = out->n_labels;
+    write_json_device(E, s, path, t0, now_ms());
+    rc = RS_OK;
+  } catch (const RsError &e) {
+    set_error(e.what());
+    rc = e.code;
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    rc = RS_E_INTERNAL;
+  }
+  rs_engine_destroy(E);
+  return rc;
+}
+
+int rs_write_substitution_json_device(int device, const char *path, const rs_output *out) {
+  if (!path || !out || (out->n_log && (!out->log_from || !out->log_to.ptr))) {
+    set_error("rs_write_substitution_json_device: null argument");
+    return RS_E_INVALID;
+  }
+  rs_engine *E = nullptr;
+  int rc = rs_engine_create(device, &E);
+  if (rc) return rc;
+  try {
+    HC(hipSetDevice(E->device));
+    const double t0 = now_ms();
+    JsonHostPart hp;
+    JsonSrc s;
+    s.n = out->n_log;
+    s.nparts = 1;
+    json_host_part(nullptr, 0, out->log_to, s.n, nullptr, hp);
+    json_upload_part(E, hp, s.n, "json.in.log", 0, s);
+    if (s.n) {
+      uint32_t *from = E->SA.get<uint32_t>("json.in.from", s.n);
+      HC(hipMemcpyAsync(from, out->log_from, 4 * s.n, hipMemcpyHostToDevice, E->st));
+      s.from = from;
+    }
+    HC(hipStreamSynchronize(E->st));
+    write_json_device(E, s, path, t0, now_ms());
     rc = RS_OK;
   } catch (const RsError &e) {
     set_error(e.what());

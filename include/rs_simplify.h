@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 11
+#define RS_ABI_VERSION 12
 
 enum rs_status {
   RS_OK = 0,
@@ -268,6 +268,19 @@ typedef struct rs_stats {
   double sym_out_ms;
 } rs_stats;
 
+/* ABI 12: the last rs_engine_write_constraints_json / rs_engine_write_substitution_json on the engine,
+ * whichever came last -- the whole call; the upload (the log's; 0 for the constraints file, whose input
+ * is resident); both kernel passes, the scans and the read-back of the verdict; the image's D2H and the
+ * file (creating it included).  in_ms + kernel_ms + out_ms = write_ms.  bytes: the image, the file
+ * without its opening and closing strings. */
+typedef struct rs_json_stats {
+  double write_ms;
+  double in_ms;
+  double kernel_ms;
+  double out_ms;
+  uint64_t bytes;
+} rs_json_stats;
+
 typedef struct rs_engine rs_engine;
 
 const char *rs_last_error(void);
@@ -417,6 +430,40 @@ int rs_write_constraints_json(const char *path, const rs_output *out);
 /* --simplification_substitution: <prefix>_substitutions.json (json_porting.rs:28-33
  * port_substitution, json_writer.rs:94-131 SubstitutionJSON) from out->log_*, original ids. */
 int rs_write_substitution_json(const char *path, const rs_output *out);
+/* ABI 12: the same two files written on the device (csrc/json_write.hpp): every entry's text length is
+ * known from its own 36 bytes, one prefix sum per part places every byte, a workgroup per chunk of
+ * RS_JSON_CHUNK output bytes (a power of two, rounded down, 64 .. 65536; read on every call) converts the
+ * values (256-bit binary -> decimal) and builds its piece of the image, and the image leaves through the
+ * buffers and pwrite threads of rs_engine_write_r1cs.  Positions are 64-bit; the image is resident on the
+ * device (RS_E_OOM_DEVICE if it does not fit).
+ * rs_engine_write_constraints_json reads the engine's resident result (what rs_engine_write_r1cs reads)
+ * and writes the bytes rs_write_constraints_json writes over rs_engine_fetch's output.
+ * rs_engine_write_substitution_json sends the engine's substitution log up through pinned staging buffers
+ * and writes the bytes rs_write_substitution_json writes over the fetched output; after a run without
+ * rs_flags.emit_substitution_log that is `{\n}`.
+ * The one-shots make and destroy an engine and upload what they need of `out`:
+ * rs_write_constraints_json_device reads n_constraints, a / b / c with their {a,b,c}_len / {a,b,c}_jump
+ * arrays, n_labels and label_to_wire; rs_write_substitution_json_device reads ONLY n_log, log_from and
+ * log_to.  Both accept either row layout: the rs_output rs_engine_simplify returns works as it is.
+ * The contract: the device output equals the host writer's byte for byte for every rs_output whose row
+ * parts have strictly ascending mapped keys (label_to_wire[col] in the constraints file, col in the log)
+ * -- every result of this library does: rows hold sorted distinct keys and label_to_wire is the
+ * order-preserving rank of the kept signals.  A row part out of order (or with a key twice) is
+ * RS_E_INVALID -- deliberately stricter than the host, which sorts.  A key at or past n_labels, or one
+ * whose label_to_wire is negative ("constraint mentions a removed signal"), is RS_E_INTERNAL, as with the
+ * host writer, and wins over the order error.  Malformed row pointers or a row layout that reaches past
+ * the block's entries are RS_E_INVALID.  The verdict is known after the first kernel pass and one
+ * read-back, before `path` is opened: a refused call leaves no file, and the engine stays usable.
+ * RS_E_INVALID too for a null argument and for an engine without a result.  RS_WRITER_HOST (environment)
+ * routes both engine calls to the host writers over the fetched result.  On a sharded engine every rank
+ * holds the whole result and the whole log after a run, so any rank may call them (they are no
+ * collectives) and writes the whole file.  RS_E_NODEVICE without a gfx950 device: there is no CPU
+ * fallback.  Times in rs_json_stats (rs_engine_json_stats); rs_stats is unchanged. */
+int rs_engine_write_constraints_json(rs_engine *eng, const char *path);
+int rs_engine_write_substitution_json(rs_engine *eng, const char *path);
+int rs_write_constraints_json_device(int device, const char *path, const rs_output *out);
+int rs_write_substitution_json_device(int device, const char *path, const rs_output *out);
+int rs_engine_json_stats(rs_engine *eng, rs_json_stats *st);
 
 /* Seeded synthetic --O0 systems for benchmarks/tests (see DESIGN.md "Workloads").
  * kind: 0 = mixed (metric circuit, BASELINE configs[4]), 1 = purely linear (configs[1]), 2 = chain

@@ -1,10 +1,10 @@
-//! Raw bindings of `include/rs_simplify.h` (ABI 11), one item per C declaration, same order and
+//! Raw bindings of `include/rs_simplify.h` (ABI 12), one item per C declaration, same order and
 //! layout.  The safe wrapper a caller uses is `constraint_list_glue.rs` (the body that replaces
 //! `constraint_list::constraint_simplification::simplification`, constraint_simplification.rs:442).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RS_ABI_VERSION: c_int = 11;
+pub const RS_ABI_VERSION: c_int = 12;
 pub const RS_COMM_ID_BYTES: usize = 128;
 
 pub const RS_OK: c_int = 0;
@@ -228,6 +228,16 @@ pub struct rs_stats {
     pub sym_out_ms: f64,
 }
 
+/// ABI 12: the last device JSON writer call of either kind on an engine (in + kernel + out = write).
+#[repr(C)]
+pub struct rs_json_stats {
+    pub write_ms: f64,
+    pub in_ms: f64,
+    pub kernel_ms: f64,
+    pub out_ms: f64,
+    pub bytes: u64,
+}
+
 #[repr(C)]
 pub struct rs_engine {
     _private: [u8; 0],
@@ -279,6 +289,14 @@ extern "C" {
     pub fn rs_write_sym_device(device: c_int, o0_sym: *const c_char, path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_write_constraints_json(path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_write_substitution_json(path: *const c_char, out: *const rs_output) -> c_int;
+    /// ABI 12: the same two files formatted on the device from the engine's last result and log (a row part
+    /// whose mapped keys are not strictly ascending is RS_E_INVALID; a refused call leaves no file) ...
+    pub fn rs_engine_write_constraints_json(eng: *mut rs_engine, path: *const c_char) -> c_int;
+    pub fn rs_engine_write_substitution_json(eng: *mut rs_engine, path: *const c_char) -> c_int;
+    /// ... and the one-shots over an `rs_output` in either row layout.
+    pub fn rs_write_constraints_json_device(device: c_int, path: *const c_char, out: *const rs_output) -> c_int;
+    pub fn rs_write_substitution_json_device(device: c_int, path: *const c_char, out: *const rs_output) -> c_int;
+    pub fn rs_engine_json_stats(eng: *mut rs_engine, st: *mut rs_json_stats) -> c_int;
     pub fn rs_synth(kind: u32, rows: u64, seed: u64, prime_id: u32, inp: *mut *mut rs_input) -> c_int;
     pub fn rs_flatten_dag(device: c_int, dag: *const rs_dag, inp: *mut *mut rs_input) -> c_int;
     /// The same into the engine's page-locked buffers (the view lives until the next call on `eng`).
