@@ -146,6 +146,31 @@ class RsJsonStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RsWitness(C.Structure):
+    """rs_witness: n values of 4 limbs (canonical); n8 is the value width of its .wtns file."""
+    _fields_ = [("prime_id", C.c_uint32), ("prime", C.c_uint64 * 4), ("n8", C.c_uint32), ("n", C.c_uint64),
+                ("val", C.POINTER(C.c_uint64))]
+
+
+WIT_INPUT, WIT_OUTPUT, WIT_LOG = 1, 2, 4
+WIT_CLASSES = ("cons_eq", "eq", "linear", "nonlinear", "output", "log")   # RS_WITC_*, in order
+
+
+class RsWitnessReport(C.Structure):
+    """rs_witness_report: per class (WIT_CLASSES) the rows checked, those that do not hold and the
+    smallest failing index (U64_MAX: none)."""
+    _fields_ = [("checked", C.c_uint64 * 6), ("failed", C.c_uint64 * 6), ("first_failed", C.c_uint64 * 6),
+                ("in_ms", C.c_double), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("in_ms", "kernel_ms", "total_ms")}
+        for i, nm in enumerate(WIT_CLASSES):
+            first = int(self.first_failed[i])
+            d[nm] = {"checked": int(self.checked[i]), "failed": int(self.failed[i]),
+                     "first_failed": None if first == U64_MAX else first}
+        return d
+
+
 class RsDag(C.Structure):
     """rs_dag: the component DAG rs_flatten_dag expands."""
     _fields_ = [("prime_id", C.c_uint32), ("prime", C.c_uint64 * 4),
@@ -204,6 +229,15 @@ SYMBOLS = [
     ("rs_write_constraints_json_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(RsOutput)]),
     ("rs_write_substitution_json_device", C.c_int, [C.c_int, C.c_char_p, C.POINTER(RsOutput)]),
     ("rs_engine_json_stats", C.c_int, [C.c_void_p, C.POINTER(RsJsonStats)]),
+    ("rs_read_wtns", C.c_int, [C.c_char_p, C.POINTER(C.POINTER(RsWitness))]),
+    ("rs_witness_free", None, [C.POINTER(RsWitness)]),
+    ("rs_write_wtns", C.c_int, [C.c_char_p, C.POINTER(RsWitness), C.POINTER(RsOutput)]),
+    ("rs_check_witness", C.c_int, [C.POINTER(RsInput), C.POINTER(RsOutput), C.POINTER(RsWitness), C.c_uint32,
+                                   C.POINTER(RsWitnessReport)]),
+    ("rs_engine_load_witness", C.c_int, [C.c_void_p, C.POINTER(RsWitness)]),
+    ("rs_engine_load_wtns", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rs_engine_check_witness", C.c_int, [C.c_void_p, C.POINTER(RsInput), C.c_uint32, C.POINTER(RsWitnessReport)]),
+    ("rs_engine_write_wtns", C.c_int, [C.c_void_p, C.c_char_p]),
 ]
 
 _LIB = None
@@ -371,6 +405,25 @@ class Engine:
         check(lib().rs_engine_write_substitution_json(self._h, path.encode()))
         return self.json_stats().write_ms
 
+    def load_witness(self, w):
+        """rs_engine_load_witness: `w` (a Witness or an RsWitness) resident on the engine until the next load."""
+        check(lib().rs_engine_load_witness(self._h, C.byref(w.c if isinstance(w, Witness) else w)))
+
+    def load_wtns(self, path: str):
+        """rs_engine_load_wtns: the .wtns at `path` streamed to the device and made resident."""
+        check(lib().rs_engine_load_wtns(self._h, path.encode()))
+
+    def check_witness(self, what: int, inp: RsInput | None = None) -> RsWitnessReport:
+        """rs_engine_check_witness: the resident witness against `inp` (WIT_INPUT), the last result
+        (WIT_OUTPUT) and the last run's substitution log (WIT_LOG), evaluated on the device."""
+        rep = RsWitnessReport()
+        check(lib().rs_engine_check_witness(self._h, C.byref(inp) if inp is not None else None, what, C.byref(rep)))
+        return rep
+
+    def write_wtns(self, path: str):
+        """rs_engine_write_wtns: the resident witness projected onto the last result's wires."""
+        check(lib().rs_engine_write_wtns(self._h, path.encode()))
+
     def json_stats(self) -> RsJsonStats:
         s = RsJsonStats()
         check(lib().rs_engine_json_stats(self._h, C.byref(s)))
@@ -421,6 +474,84 @@ class Output:
         if self.ptr:
             lib().rs_output_free(self.ptr)
             self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def check_witness(w, what: int, inp: RsInput | None = None, out: RsOutput | None = None) -> RsWitnessReport:
+    """rs_check_witness: the host evaluation of `w` (a Witness or an RsWitness)."""
+    rep = RsWitnessReport()
+    check(lib().rs_check_witness(C.byref(inp) if inp is not None else None, C.byref(out) if out is not None else None,
+                                 C.byref(w.c if isinstance(w, Witness) else w), what, C.byref(rep)))
+    return rep
+
+
+def field_size_bytes(p: int) -> int:
+    """The .r1cs header's field size (r1cs_porting.rs:6-10): the .wtns value width n8."""
+    bits = p.bit_length()
+    return bits // 8 if bits % 64 == 0 else (bits // 64 + 1) * 8
+
+
+class Witness:
+    """An rs_witness: read from a .wtns (library-owned) or built from Python ints (numpy-owned)."""
+
+    def __init__(self, ptr=None, struct=None, keep=None):
+        self.ptr, self._struct, self._keep = ptr, struct, keep
+
+    @property
+    def c(self) -> RsWitness:
+        if self.ptr:
+            s = self.ptr.contents
+            s._owner = self
+            return s
+        return self._struct
+
+    @staticmethod
+    def read(path: str) -> "Witness":
+        p = C.POINTER(RsWitness)()
+        check(lib().rs_read_wtns(path.encode(), C.byref(p)))
+        return Witness(ptr=p)
+
+    @staticmethod
+    def from_ints(values, prime: int, n8: int | None = None) -> "Witness":
+        """`values` (each 0 <= v < 2^256) over the field of `prime` (an int, or one of PRIME_IDS' names)."""
+        w = RsWitness()
+        if isinstance(prime, str):
+            raise TypeError("prime is the modulus; its name is found from it")
+        arr = np.zeros(4 * max(len(values), 1), np.uint64)
+        for i, v in enumerate(values):
+            for k in range(4):
+                arr[4 * i + k] = (v >> (64 * k)) & U64_MAX
+        w.prime_id = RS_PRIME_CUSTOM
+        for k in range(4):
+            w.prime[k] = (prime >> (64 * k)) & U64_MAX
+        w.n8 = field_size_bytes(prime) if n8 is None else n8
+        w.n = len(values)
+        w.val = arr.ctypes.data_as(C.POINTER(C.c_uint64))
+        return Witness(struct=w, keep=arr)
+
+    def values(self):
+        c = self.c
+        n = int(c.n)
+        a = np.ctypeslib.as_array(c.val, shape=(max(4 * n, 1),))
+        return [sum(int(a[4 * i + k]) << (64 * k) for k in range(4)) for i in range(n)]
+
+    def prime(self) -> int:
+        return sum(int(self.c.prime[k]) << (64 * k) for k in range(4))
+
+    def write(self, path: str, out: RsOutput | None = None):
+        """rs_write_wtns: as it is, or projected onto `out`'s wires."""
+        check(lib().rs_write_wtns(path.encode(), C.byref(self.c), C.byref(out) if out is not None else None))
+
+    def free(self):
+        if self.ptr:
+            lib().rs_witness_free(self.ptr)
+            self.ptr = None
+        self._struct = self._keep = None
 
     def __del__(self):
         try:

@@ -2,7 +2,7 @@
 //
 //   circom-simplify <in_O0.r1cs> [<in_O0.sym>] --O1|--O2|--O2round N
 //                   [--use_old_simplification_heuristics] [--json] [--simplification_substitution]
-//                   [--device D] [--host-reader] -o <out_prefix>
+//                   [--wtns <in_O0.wtns>] [--device D] [--host-reader] -o <out_prefix>
 //
 // Reads an --O0 export (which losslessly holds what simplification() consumes, SURVEY CS-4),
 // runs the GPU back end and writes <out_prefix>.r1cs (+ .sym), like `circom --r1cs --sym` at the
@@ -19,6 +19,16 @@
 // rs_engine_write_substitution_json, from the result and the log the run left with the engine);
 // --host-reader keeps rs_write_constraints_json / rs_write_substitution_json.  The files and the summary
 // are the same bytes either way.
+//
+// --wtns <in_O0.wtns>: the witness the --O0 circuit's generator wrote (one value per label; at --O0 wires
+// equal labels, SURVEY CS-4).  After the files are written it is checked on the input rows, the output rows
+// and -- with --simplification_substitution -- the substitution log, and its projection onto the result's
+// wires is written to <out_prefix>.wtns, the witness that fits <out_prefix>.r1cs.  On the engine path the
+// witness is streamed to the device, evaluated and projected there (rs_engine_load_wtns,
+// rs_engine_check_witness, rs_engine_write_wtns); --host-reader uses rs_read_wtns, rs_check_witness and
+// rs_write_wtns: the same file and the same messages.  An input row that fails means the witness is not one
+// of this circuit: exit status 3, no .wtns.  The input holding but an output row or log entry failing is a
+// simplifier bug: exit status 4, no .wtns.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +38,7 @@
 #include "../../include/rs_simplify.h"
 
 int main(int argc, char **argv) {
-  const char *in_r1cs = nullptr, *in_sym = nullptr;
+  const char *in_r1cs = nullptr, *in_sym = nullptr, *in_wtns = nullptr;
   std::string out;
   bool json = false, host_reader = false;
   rs_flags fl;
@@ -47,6 +57,7 @@ int main(int argc, char **argv) {
     else if (a == "--json") json = true;
     else if (a == "--host-reader") host_reader = true;
     else if (a == "--simplification_substitution") fl.emit_substitution_log = 1;
+    else if (a == "--wtns" && i + 1 < argc) in_wtns = argv[++i];
     else if (a == "--device" && i + 1 < argc) fl.device = atoi(argv[++i]);
     else if (a == "-o" && i + 1 < argc) out = argv[++i];
     else if (!in_r1cs) in_r1cs = argv[i];
@@ -55,7 +66,7 @@ int main(int argc, char **argv) {
   }
   if (!in_r1cs || out.empty()) {
     fprintf(stderr, "usage: circom-simplify in_O0.r1cs [in_O0.sym] --O1|--O2|--O2round N [--json] "
-                    "[--simplification_substitution] [--host-reader] -o out_prefix\n");
+                    "[--simplification_substitution] [--wtns in_O0.wtns] [--host-reader] -o out_prefix\n");
     return 2;
   }
   // (`in` and `o` are the library's either way: owned by the engine, or freed below)
@@ -88,6 +99,34 @@ int main(int argc, char **argv) {
   if (fl.emit_substitution_log && (eng ? rs_engine_write_substitution_json(eng, (out + "_substitutions.json").c_str()) : rs_write_substitution_json((out + "_substitutions.json").c_str(), o))) {
     fprintf(stderr, "error: %s\n", rs_last_error());
     return 1;
+  }
+  if (in_wtns) {  // the witness: checked on the input, the output and the log, then projected onto the wires
+    const uint32_t what = RS_WIT_INPUT | RS_WIT_OUTPUT | (fl.emit_substitution_log ? RS_WIT_LOG : 0u);
+    rs_witness_report rep;
+    rs_witness *w = nullptr;
+    int rc = eng ? rs_engine_load_wtns(eng, in_wtns) : rs_read_wtns(in_wtns, &w);
+    if (!rc) rc = eng ? rs_engine_check_witness(eng, in, what, &rep) : rs_check_witness(in, o, w, what, &rep);
+    if (rc) { fprintf(stderr, "error: %s\n", rs_last_error()); rs_witness_free(w); return 1; }
+    static const char *cls[RS_WITC_COUNT] = {"constant-equality input row", "equality input row", "linear input row",
+                                             "non-linear input row", "output row", "substitution"};
+    for (int c = 0; c < RS_WITC_COUNT; ++c)
+      if (rep.failed[c]) {
+        const bool input = c <= RS_WITC_NONLINEAR;
+        fprintf(stderr, "witness: %s %llu does not hold (%llu of %llu fail): %s; no .wtns written\n", cls[c],
+                (unsigned long long)rep.first_failed[c], (unsigned long long)rep.failed[c], (unsigned long long)rep.checked[c],
+                input ? "the witness is not one of this circuit" : "the input rows hold, so this is a simplifier bug");
+        rs_witness_free(w);
+        return input ? 3 : 4;
+      }
+    rc = eng ? rs_engine_write_wtns(eng, (out + ".wtns").c_str()) : rs_write_wtns((out + ".wtns").c_str(), w, o);
+    rs_witness_free(w);
+    if (rc) { fprintf(stderr, "error: %s\n", rs_last_error()); return 1; }
+    const unsigned long long n_in = rep.checked[RS_WITC_CONS_EQ] + rep.checked[RS_WITC_EQ] + rep.checked[RS_WITC_LINEAR] + rep.checked[RS_WITC_NONLINEAR];
+    if (fl.emit_substitution_log)
+      fprintf(stderr, "witness: %llu input rows, %llu output rows, %llu substitutions hold\n", n_in,
+              (unsigned long long)rep.checked[RS_WITC_OUTPUT], (unsigned long long)rep.checked[RS_WITC_LOG]);
+    else
+      fprintf(stderr, "witness: %llu input rows, %llu output rows hold\n", n_in, (unsigned long long)rep.checked[RS_WITC_OUTPUT]);
   }
   // constraint_writers/src/log_writer.rs:24-47
   uint64_t nl = 0, l = 0;

@@ -33,6 +33,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "host_common.hpp"
+#include "wtns_io.hpp"
 #include "kernels.hpp"
 #include "frames_wave.hpp"
 #include "spec_loop.hpp"
@@ -259,7 +260,7 @@ struct rs_engine {
   hipStream_t st2 = nullptr;  // the largest clusters' elimination chain runs here, beside the rest
   hipEvent_t ev[kEvCount] = {};  // (enum Ev)
   Arena A;
-  Arena SA;  // rs_engine_write_sym's and the JSON writers' buffers (sym.*, json.*): apart from A, whose generation guards the result views (fin_gen)
+  Arena SA;  // rs_engine_write_sym's, the JSON writers' and the witness's buffers (sym.*, json.*, wit.*): apart from A, whose generation guards the result views (fin_gen)
   bool loaded = false;
   bool have_result = false;
   int fault_at = 0;  // rs_engine_inject_fault: 1 = throw at the start of the first elimination round
@@ -281,6 +282,13 @@ struct rs_engine {
   uint64_t n_wires = 0, npiw = 0;
   rs_stats stats{};
   rs_json_stats jstats{};  // the last JSON writer call of either kind
+  // the resident witness (witness.hpp): wit_n values in Montgomery form of its own field WF in SA "wit.w",
+  // until the next load; wit_n8: the value width of its file (what rs_engine_write_wtns writes)
+  bool wit_on = false;
+  uint64_t wit_n = 0;
+  uint32_t wit_n8 = 0, wit_prime_id = 0;
+  uint64_t wit_prime[4] = {0, 0, 0, 0};
+  FieldP WF;
   // sharded elimination: this engine is rank `comm->rank` of `comm->world`
   std::unique_ptr<rs::Comm> comm;
   // substitution log of the last run (rs_flags.emit_substitution_log), canonical values
@@ -635,6 +643,7 @@ static void load_order_collectives(rs_engine *E) {
 // After a failed call: the copy stream may still be reading the caller's buffers.
 static void snap_join(rs_engine *E);
 static void *pin_get(rs_engine *E, int slot, size_t bytes);
+static void ensure_csr(rs_engine *E);
 static void load_abort(rs_engine *E) {
   if (E->stc) (void)hipStreamSynchronize(E->stc);
   snap_join(E);
@@ -818,6 +827,7 @@ struct ImageOut {
 #include "r1cs_read.hpp"
 #include "sym_write.hpp"
 #include "json_write.hpp"
+#include "witness.hpp"
 #include "output.hpp"
 __global__ void k_pack3(const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n, U3 *out) {
   for (uint64_t i = gtid(); i < n; i += gstride()) out[i] = U3{a[i], b[i], c[i]};
@@ -3703,6 +3713,69 @@ int rs_write_substitution_json_device(int device, const char *path, const rs_out
   }
   rs_engine_destroy(E);
   return rc;
+}
+
+// ---- the witness on the device (witness.hpp)
+namespace rs {
+// the bracket of a witness call: nothing of it may still be queued when it fails
+extern "C++" template <class F>
+static int wit_call(rs_engine *E, F &&f) {
+  CpuNear cpu_near_(E);  // the caller's affinity is restored on return
+  try {
+    HC(hipSetDevice(E->device));
+    snap_join(E);  // no D2H of a result still uses the copy stream
+    f();
+    return RS_OK;
+  } catch (const RsError &e) {
+    (void)hipStreamSynchronize(E->stc);
+    (void)hipStreamSynchronize(E->st);
+    set_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    (void)hipStreamSynchronize(E->stc);
+    (void)hipStreamSynchronize(E->st);
+    set_error(e.what());
+    return RS_E_INTERNAL;
+  }
+}
+}  // namespace rs
+
+int rs_engine_load_witness(rs_engine *E, const rs_witness *w) {
+  if (!E || !w || (w->n && !w->val)) { set_error("rs_engine_load_witness: null argument"); return RS_E_INVALID; }
+  return wit_call(E, [&] {
+    uint64_t p[4];
+    if (!wtns::witness_prime(w, p)) throw RsError(RS_E_INVALID, "rs_engine_load_witness: bad prime or field size");
+    if (w->n == 0 || w->n > 0x7fffffffull) throw RsError(RS_E_INVALID, "rs_engine_load_witness: the witness needs 1 .. 2^31 - 1 values");
+    const uint64_t *val = w->val;
+    wit_upload(E, w->n, 32, w->n8, p, wtns::prime_id_of(p), [val](uint8_t *dst, uint64_t i0, uint64_t cnt) {
+      memcpy(dst, val + 4 * i0, 32 * cnt);
+      return true;
+    });
+  });
+}
+
+int rs_engine_load_wtns(rs_engine *E, const char *path) {
+  if (!E || !path) { set_error("rs_engine_load_wtns: null argument"); return RS_E_INVALID; }
+  return wit_call(E, [&] {
+    wtns::Fd f{-1};
+    wtns::Head H;
+    if (!wtns::open_head(path, f, H)) throw RsError(RS_E_INVALID, rs_last_error());
+    if (H.n == 0 || H.n > 0x7fffffffull) throw RsError(RS_E_INVALID, "rs_engine_load_wtns: the witness needs 1 .. 2^31 - 1 values");
+    const int fd = f.fd;
+    const uint64_t off2 = H.off2, n8 = H.n8;
+    wit_upload(E, H.n, H.n8, H.n8, H.prime, H.prime_id,
+               [fd, off2, n8](uint8_t *dst, uint64_t i0, uint64_t cnt) { return wtns::pread_all(fd, dst, cnt * n8, off2 + i0 * n8); });
+  });
+}
+
+int rs_engine_check_witness(rs_engine *E, const rs_input *in, uint32_t what, rs_witness_report *rep) {
+  if (!E || !rep) { set_error("rs_engine_check_witness: null argument"); return RS_E_INVALID; }
+  return wit_call(E, [&] { check_witness_device(E, in, what, rep); });
+}
+
+int rs_engine_write_wtns(rs_engine *E, const char *path) {
+  if (!E || !path) { set_error("rs_engine_write_wtns: null argument"); return RS_E_INVALID; }
+  return wit_call(E, [&] { write_wtns_device(E, path); });
 }
 
 void *rs_host_alloc(uint64_t bytes) {

@@ -11,6 +11,8 @@
 //   rs_write_constraints_json / rs_write_substitution_json : the --json and
 //                     --simplification_substitution outputs (constraint_list/src/json_porting.rs,
 //                     constraint_writers/src/json_writer.rs).
+//   rs_read_wtns / rs_write_wtns / rs_check_witness : the .wtns witness file and the host evaluation
+//                     of a witness (wtns_io.hpp, header-only; the wrappers are at the end of this file).
 #include <algorithm>
 #include <cstdio>
 #include <fstream>
@@ -21,6 +23,7 @@
 #include <unistd.h>
 
 #include "host_common.hpp"
+#include "wtns_io.hpp"
 
 namespace rs {
 
@@ -627,3 +630,11 @@ int rs_write_sym(const char *o0_sym, const char *path, const rs_output *out) {
 }
 
 }  // extern "C"
+
+// ---- the witness (wtns_io.hpp): the .wtns reader and writer, the host evaluation
+int rs_read_wtns(const char *path, rs_witness **w) { return rs::wtns::read_wtns(path, w); }
+void rs_witness_free(rs_witness *w) { rs::wtns::witness_free(w); }
+int rs_write_wtns(const char *path, const rs_witness *w, const rs_output *out) { return rs::wtns::write_wtns(path, w, out); }
+int rs_check_witness(const rs_input *in, const rs_output *out, const rs_witness *w, uint32_t what, rs_witness_report *rep) {
+  return rs::wtns::check_witness(in, out, w, what, rep);
+}

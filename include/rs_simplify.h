@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 12
+#define RS_ABI_VERSION 13
 
 enum rs_status {
   RS_OK = 0,
@@ -464,6 +464,95 @@ int rs_engine_write_substitution_json(rs_engine *eng, const char *path);
 int rs_write_constraints_json_device(int device, const char *path, const rs_output *out);
 int rs_write_substitution_json_device(int device, const char *path, const rs_output *out);
 int rs_engine_json_stats(rs_engine *eng, rs_json_stats *st);
+
+/* ---- ABI 13: the witness.  A .wtns file (what the reference's generated programs write:
+ * code_producers/src/c_elements/common/main.cpp writeBinWitness, and the wasm witness_calculator.js)
+ * read, checked against the circuit and the result, and projected onto the result's wires.  At --O0
+ * wires equal labels, so the user's witness generator writes one value per label; after --O1 / --O2 the
+ * .r1cs is numbered by wire and label_to_wire says which values stay.
+ * File format, all integers little endian: `wtns`, u32 version = 2, u32 nSections, then sections
+ * (u32 id, u64 length, body): id 1 = u32 n8, the prime in n8 bytes, u32 nVars; id 2 = nVars values of
+ * n8 bytes, each canonical.  n8 is the .r1cs header's field size (8 for goldilocks, 32 for the 256-bit
+ * primes).
+ * rs_witness: n values of 4 limbs (canonical, little endian, like rs_lc.val); prime[] is always filled,
+ * prime_id is RS_PRIME_CUSTOM when the prime is none of the eight; n8 is the file's value width. */
+typedef struct rs_witness {
+  uint32_t prime_id;
+  uint64_t prime[4];
+  uint32_t n8;
+  uint64_t n;
+  uint64_t *val;
+} rs_witness;
+
+#define RS_WIT_INPUT 1u  /* the rows of the caller's rs_input (four classes)  */
+#define RS_WIT_OUTPUT 2u /* the rows of the result                            */
+#define RS_WIT_LOG 4u    /* the entries of the substitution log               */
+/* The classes of rs_witness_report, in order. */
+enum rs_witness_class {
+  RS_WITC_CONS_EQ = 0, /* rs_input.cons_eq: holds iff C.w = 0                       */
+  RS_WITC_EQ = 1,      /* rs_input.eq: C.w = 0                                      */
+  RS_WITC_LINEAR = 2,  /* rs_input.linear: C.w = 0                                  */
+  RS_WITC_NONLINEAR = 3, /* rs_input.nl_{a,b,c}: (A.w)(B.w) - C.w = 0               */
+  RS_WITC_OUTPUT = 4,  /* rs_output.{a,b,c}: (A.w)(B.w) - C.w = 0                   */
+  RS_WITC_LOG = 5,     /* log entry i: w[log_from[i]] = log_to[i].w                 */
+  RS_WITC_COUNT = 6
+};
+/* Per class: the rows evaluated (0 for a class not asked for), how many do not hold, and the smallest
+ * failing index within the class (UINT64_MAX when none failed).  in_ms: the uploads (the caller's input,
+ * the log); kernel_ms: the evaluation; total_ms: the whole call.  The host check leaves in_ms 0. */
+typedef struct rs_witness_report {
+  uint64_t checked[6], failed[6], first_failed[6];
+  double in_ms, kernel_ms, total_ms;
+} rs_witness_report;
+
+/* Reads a .wtns (library-owned arrays: rs_witness_free).  Sections are found by walking the section
+ * table; unknown ids are skipped; sections 1 and 2 come in either order.  RS_E_INVALID, with a message
+ * naming the cause, for: bad magic; a version other than 2; a missing or duplicated section 1 or 2; a
+ * section running past the file; n8 no multiple of 8 or outside 8..32; section 1 not 8 + n8 bytes; a
+ * prime that is even or below 3; section 2's length not n8 * nVars; a value >= the prime.  Every size is
+ * checked before the allocation it guards. */
+int rs_read_wtns(const char *path, rs_witness **w);
+void rs_witness_free(rs_witness *w);
+/* Writes a .wtns.  out == NULL: `w` as it is.  Otherwise the projection onto the result's wires:
+ * out->n_wires values, value label_to_wire[s] = w[s] for every label s with a wire; of `out` only
+ * label_to_wire, n_labels and n_wires are read, so either row layout works.  RS_E_INVALID for a null
+ * argument, a bad n8 or prime, a value >= the prime, w->n != out->n_labels or a wire >= n_wires.
+ * (rs_output carries no prime: the engine call below is the one that refuses a witness of another field.) */
+int rs_write_wtns(const char *path, const rs_witness *w, const rs_output *out);
+/* The host evaluation of a witness, in plain 256-bit host arithmetic (csrc/wtns_io.hpp): `what` is an OR
+ * of RS_WIT_*; `in` may be NULL without RS_WIT_INPUT, `out` without RS_WIT_OUTPUT and RS_WIT_LOG.  Key 0
+ * is the constant.  Returns RS_OK whenever the evaluation ran: rows that do not hold are a finding in
+ * `rep`, not an error.  RS_E_INVALID for: a null argument that is needed; w[0] != 1; a value >= the
+ * prime; w->n != in->max_signal (RS_WIT_INPUT) or != out->n_labels (RS_WIT_OUTPUT, RS_WIT_LOG); a
+ * witness prime that is not the input's; malformed row pointers; a key >= w->n.  `out` in either row
+ * layout.  Coefficients are taken as canonical (every input and result of this library is). */
+int rs_check_witness(const rs_input *in, const rs_output *out, const rs_witness *w, uint32_t what, rs_witness_report *rep);
+/* The same on the device (csrc/witness.hpp).  rs_engine_load_witness / rs_engine_load_wtns make a witness
+ * resident on the engine until the next load (in the writers' arena: nothing of a result moves); load_wtns
+ * parses the two small header pieces on the host and streams section 2 through the pinned staging
+ * buffers, each widened, range-checked (value >= the prime, w[0] != 1: RS_E_INVALID, nothing stays
+ * resident) and stored in Montgomery form behind its copy.  A load needs neither an input nor a result.
+ * rs_engine_check_witness evaluates the resident witness: RS_WIT_INPUT over the caller's `in` (host
+ * arrays, uploaded block by block; the engine's own copy of a loaded input is not read), RS_WIT_OUTPUT
+ * over the last result's resident rows, RS_WIT_LOG over the last run's substitution log.  One evaluator
+ * serves all: a workgroup per chunk of RS_WIT_CHUNK consecutive entries of a part (a power of two,
+ * rounded down, 64 .. 8192, default 1024; read on every call), a segmented sum per row, rows that cross a chunk border
+ * summed from per-chunk partials in chunk order; no atomics on field values, so the report is
+ * deterministic and equals rs_check_witness's over the fetched result.
+ * RS_E_INVALID for: a null argument; no resident witness; RS_WIT_INPUT without `in`; RS_WIT_OUTPUT or
+ * RS_WIT_LOG without a result; RS_WIT_LOG after a run without rs_flags.emit_substitution_log; a witness
+ * whose n is not the labels of what is checked, or whose prime is not its prime; malformed row pointers
+ * of `in`; a key >= the labels.  The engine stays usable after each.  On a sharded engine every rank
+ * checks its own complete copy (no collective), like rs_engine_write_r1cs.
+ * rs_engine_write_wtns: the resident witness projected onto the last result's wires, the bytes
+ * rs_write_wtns(path, w, fetched output) writes; the image is built on the device (a lane per label with
+ * a wire stores its value, canonical and narrowed to n8 bytes, at n8 * label_to_wire[s]) and leaves
+ * through the buffers and pwrite threads of rs_engine_write_r1cs.  RS_E_INVALID without a result, without
+ * a witness, or for a witness of another size or prime.  RS_E_NODEVICE without a gfx950 device. */
+int rs_engine_load_witness(rs_engine *eng, const rs_witness *w);
+int rs_engine_load_wtns(rs_engine *eng, const char *path);
+int rs_engine_check_witness(rs_engine *eng, const rs_input *in, uint32_t what, rs_witness_report *rep);
+int rs_engine_write_wtns(rs_engine *eng, const char *path);
 
 /* Seeded synthetic --O0 systems for benchmarks/tests (see DESIGN.md "Workloads").
  * kind: 0 = mixed (metric circuit, BASELINE configs[4]), 1 = purely linear (configs[1]), 2 = chain

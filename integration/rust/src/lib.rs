@@ -1,10 +1,10 @@
-//! Raw bindings of `include/rs_simplify.h` (ABI 12), one item per C declaration, same order and
+//! Raw bindings of `include/rs_simplify.h` (ABI 13), one item per C declaration, same order and
 //! layout.  The safe wrapper a caller uses is `constraint_list_glue.rs` (the body that replaces
 //! `constraint_list::constraint_simplification::simplification`, constraint_simplification.rs:442).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RS_ABI_VERSION: c_int = 12;
+pub const RS_ABI_VERSION: c_int = 13;
 pub const RS_COMM_ID_BYTES: usize = 128;
 
 pub const RS_OK: c_int = 0;
@@ -228,6 +228,37 @@ pub struct rs_stats {
     pub sym_out_ms: f64,
 }
 
+/// ABI 13: a witness, `n` values of 4 limbs (canonical); `n8` is the value width of its .wtns file.
+#[repr(C)]
+pub struct rs_witness {
+    pub prime_id: u32,
+    pub prime: [u64; 4],
+    pub n8: u32,
+    pub n: u64,
+    pub val: *mut u64,
+}
+
+pub const RS_WIT_INPUT: u32 = 1;
+pub const RS_WIT_OUTPUT: u32 = 2;
+pub const RS_WIT_LOG: u32 = 4;
+pub const RS_WITC_CONS_EQ: usize = 0;
+pub const RS_WITC_EQ: usize = 1;
+pub const RS_WITC_LINEAR: usize = 2;
+pub const RS_WITC_NONLINEAR: usize = 3;
+pub const RS_WITC_OUTPUT: usize = 4;
+pub const RS_WITC_LOG: usize = 5;
+
+/// Per class (RS_WITC_*): rows evaluated, rows that do not hold, the smallest failing index (u64::MAX: none).
+#[repr(C)]
+pub struct rs_witness_report {
+    pub checked: [u64; 6],
+    pub failed: [u64; 6],
+    pub first_failed: [u64; 6],
+    pub in_ms: f64,
+    pub kernel_ms: f64,
+    pub total_ms: f64,
+}
+
 /// ABI 12: the last device JSON writer call of either kind on an engine (in + kernel + out = write).
 #[repr(C)]
 pub struct rs_json_stats {
@@ -297,6 +328,18 @@ extern "C" {
     pub fn rs_write_constraints_json_device(device: c_int, path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_write_substitution_json_device(device: c_int, path: *const c_char, out: *const rs_output) -> c_int;
     pub fn rs_engine_json_stats(eng: *mut rs_engine, st: *mut rs_json_stats) -> c_int;
+    /// ABI 13: the .wtns witness file (library-owned arrays: rs_witness_free) ...
+    pub fn rs_read_wtns(path: *const c_char, w: *mut *mut rs_witness) -> c_int;
+    pub fn rs_witness_free(w: *mut rs_witness);
+    /// ... written as it is (`out` null) or projected onto the result's wires ...
+    pub fn rs_write_wtns(path: *const c_char, w: *const rs_witness, out: *const rs_output) -> c_int;
+    /// ... the host evaluation (`what`: an OR of RS_WIT_*; failing rows are a finding in `rep`, not an error) ...
+    pub fn rs_check_witness(inp: *const rs_input, out: *const rs_output, w: *const rs_witness, what: u32, rep: *mut rs_witness_report) -> c_int;
+    /// ... and the same on the device: a witness resident on the engine, evaluated and projected there.
+    pub fn rs_engine_load_witness(eng: *mut rs_engine, w: *const rs_witness) -> c_int;
+    pub fn rs_engine_load_wtns(eng: *mut rs_engine, path: *const c_char) -> c_int;
+    pub fn rs_engine_check_witness(eng: *mut rs_engine, inp: *const rs_input, what: u32, rep: *mut rs_witness_report) -> c_int;
+    pub fn rs_engine_write_wtns(eng: *mut rs_engine, path: *const c_char) -> c_int;
     pub fn rs_synth(kind: u32, rows: u64, seed: u64, prime_id: u32, inp: *mut *mut rs_input) -> c_int;
     pub fn rs_flatten_dag(device: c_int, dag: *const rs_dag, inp: *mut *mut rs_input) -> c_int;
     /// The same into the engine's page-locked buffers (the view lives until the next call on `eng`).
