@@ -675,14 +675,22 @@ static void h2d(rs_engine *E, void *dst, const void *src, size_t bytes) {
 }
 
 // ---------------------------------------------------------------- scans
+// out[i] = zero + in[0] + .. + in[i - 1] under `op`, on stream s, nothing read back; rocprim's temporary
+// storage is the arena's buffer `tag`
+template <class T, class Op>
+static void excl_scan(Arena &A, const std::string &tag, hipStream_t s, const T *in, T *out, T zero, uint64_t n, Op op, bool size_only = false) {
+  if (!n) return;
+  size_t tb = 0;
+  HC(rocprim::exclusive_scan(nullptr, tb, in, out, zero, (size_t)n, op, s));
+  void *tmp = A.get<uint8_t>(tag, tb);
+  if (!size_only) HC(rocprim::exclusive_scan(tmp, tb, in, out, zero, (size_t)n, op, s));  // (size_only: giant_buffers, ahead of its loop)
+}
+
 constexpr size_t kPinRb = 128;  // pinned slot 18: small read-backs (one size everywhere: never reallocated)
 static uint64_t excl_scan_u64(rs_engine *E, const uint64_t *in, uint64_t *out, uint64_t n, const char *tag,
                               double *waited = nullptr) {
   if (n == 0) return 0;
-  size_t tb = 0;
-  HC(rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E->st));
-  void *tmp = E->A.get<uint8_t>(std::string("scan.tmp.") + tag, tb);
-  HC(rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E->st));
+  excl_scan(E->A, std::string("scan.tmp.") + tag, E->st, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>());
   uint64_t *h = (uint64_t *)pin_get(E, kPinRead, kPinRb) + 4;  // pinned read-back words [4..5] (no staged copy)
   HC(hipMemcpyAsync(h, in + n - 1, 8, hipMemcpyDeviceToHost, E->st));
   HC(hipMemcpyAsync(h + 1, out + n - 1, 8, hipMemcpyDeviceToHost, E->st));
@@ -707,11 +715,7 @@ static U3 excl_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, const ch
   if (n == 0 && !x_sum) return U3{0, 0, 0};
   uint64_t *h = (uint64_t *)pin_get(E, kPinRead, kPinRb) + 8;
   if (n) {
-    size_t tb = 0;
-    const U3 zero{0, 0, 0};
-    HC(rocprim::exclusive_scan(nullptr, tb, in, out, zero, (size_t)n, U3Plus(), E->st));
-    void *tmp = E->A.get<uint8_t>(std::string("scan3.tmp.") + tag, tb);
-    HC(rocprim::exclusive_scan(tmp, tb, in, out, zero, (size_t)n, U3Plus(), E->st));
+    excl_scan(E->A, std::string("scan3.tmp.") + tag, E->st, in, out, U3{0, 0, 0}, n, U3Plus());
     HC(hipMemcpyAsync(h, in + n - 1, sizeof(U3), hipMemcpyDeviceToHost, E->st));
     HC(hipMemcpyAsync(h + 3, out + n - 1, sizeof(U3), hipMemcpyDeviceToHost, E->st));
   }
@@ -724,105 +728,7 @@ static U3 excl_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, const ch
   return n ? U3{h[0] + h[3], h[1] + h[4], h[2] + h[5]} : U3{0, 0, 0};
 }
 
-// ---------------------------------------------------------------- a device image on its way to a file
-static bool pwrite_all(int fd, const uint8_t *p, uint64_t len, uint64_t off) {
-  while (len) {
-    const ssize_t w = pwrite(fd, p, len, (off_t)off);
-    if (w <= 0) return false;
-    p += w;
-    len -= (uint64_t)w;
-    off += (uint64_t)w;
-  }
-  return true;
-}
-// The way out of rs_engine_write_r1cs's and rs_engine_write_sym's images: 32 MB chunks through page-locked
-// buffers (pin slot kPinWrite) that four threads pwrite at their offsets while the next chunks' D2H run.
-// The page cache bounds it: on the GPU box's overlay file system a fresh 0.92 GB file takes 130-160 ms with
-// one or four writers (a shared mapping with four copiers: ~400 ms of page faults), the D2H ~18 ms at
-// link speed.
-struct ImageOut {
-  static constexpr uint64_t kChunk = 32ull << 20;
-  static constexpr int kBufs = 8, kThreads = 4;
-  uint8_t *pool = nullptr;
-  hipEvent_t ev[kBufs] = {};
-  ~ImageOut() {
-    for (hipEvent_t x : ev)
-      if (x) (void)hipEventDestroy(x);
-  }
-  // everything that can throw before the file exists: the pinned buffers, the events (a
-  // throw between open() and the guarded block leaked the fd or destroyed joinable threads)
-  void prepare(rs_engine *E, uint64_t bytes) {
-    const uint64_t nch = (bytes + kChunk - 1) / kChunk;
-    if (nch) pool = (uint8_t *)pin_get(E, kPinWrite, nch > 1 ? std::min<uint64_t>(nch, kBufs) * kChunk : bytes);
-    for (int b = 0; b < kBufs; ++b) HC(hipEventCreateWithFlags(&ev[b], hipEventDisableTiming));
-  }
-  // src[0, bytes) (device; its producers on `st`) -> fd at img_off; a failed write sets io_err
-  void run(hipStream_t st, int fd, const uint8_t *src, uint64_t bytes, uint64_t img_off, std::atomic<bool> &io_err) {
-    const uint64_t nch = (bytes + kChunk - 1) / kChunk;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<uint64_t> work;       // chunks whose D2H is enqueued
-    std::vector<char> written(nch, 0);
-    bool closing = false;
-    // the writer threads are joined on every way out of this scope (a throw included): closing drains
-    // them, and the guard lives after everything they reference
-    struct Writers {
-      std::vector<std::thread> th;
-      std::mutex &mu;
-      std::condition_variable &cv;
-      bool &closing;
-      std::deque<uint64_t> &work;
-      void stop(bool drop) {
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          closing = true;
-          if (drop) work.clear();
-        }
-        cv.notify_all();
-        for (auto &x : th)
-          if (x.joinable()) x.join();
-      }
-      ~Writers() { stop(true); }
-    } writers{{}, mu, cv, closing, work};
-    for (int t = 0; t < kThreads && (uint64_t)t < nch; ++t)
-      writers.th.emplace_back([&]() {
-        for (;;) {
-          uint64_t i;
-          {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return closing || !work.empty(); });
-            if (work.empty()) return;
-            i = work.front();
-            work.pop_front();
-          }
-          const uint64_t off = i * kChunk, len = std::min(kChunk, bytes - off);
-          if (hipEventSynchronize(ev[i % kBufs]) != hipSuccess) io_err = true;
-          else if (!pwrite_all(fd, pool + (i % kBufs) * kChunk, len, img_off + off)) io_err = true;
-          {
-            std::lock_guard<std::mutex> lk(mu);
-            written[i] = 1;
-          }
-          cv.notify_all();
-        }
-      });
-    for (uint64_t i = 0; i < nch; ++i) {
-      if (i >= (uint64_t)kBufs) {  // the buffer's previous chunk is on disk
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return written[i - kBufs] != 0; });
-      }
-      const uint64_t off = i * kChunk, len = std::min(kChunk, bytes - off);
-      HC(hipMemcpyAsync(pool + (i % kBufs) * kChunk, src + off, len, hipMemcpyDeviceToHost, st));
-      HC(hipEventRecord(ev[i % kBufs], st));
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        work.push_back(i);
-      }
-      cv.notify_all();
-    }
-    writers.stop(false);  // every chunk written
-  }
-};
-
+#include "stage_io.hpp"
 #include "flatten.hpp"
 #include "r1cs_read.hpp"
 #include "sym_write.hpp"
@@ -872,28 +778,15 @@ static void sort_pairs(rs_engine *E, const K *kin, K *kout, const V *vin, V *vou
 }
 // device-only exclusive scan of u64 on stream s (no read-back)
 static void dev_scan_u64(rs_engine *E, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t s, const char *tag) {
-  if (!n) return;
-  size_t tb = 0;
-  HC(rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s));
-  void *tmp = E->A.get<uint8_t>(std::string("scan.tmp.") + tag, tb);
-  HC(rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s));
+  excl_scan(E->A, std::string("scan.tmp.") + tag, s, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>());
 }
 // device-only exclusive scan of three columns at once on stream s (no read-back)
 static void dev_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, hipStream_t s, const char *tag) {
-  if (!n) return;
-  size_t tb = 0;
-  const U3 zero{0, 0, 0};
-  HC(rocprim::exclusive_scan(nullptr, tb, in, out, zero, (size_t)n, U3Plus(), s));
-  void *tmp = E->A.get<uint8_t>(std::string("scan3.tmp.") + tag, tb);
-  HC(rocprim::exclusive_scan(tmp, tb, in, out, zero, (size_t)n, U3Plus(), s));
+  excl_scan(E->A, std::string("scan3.tmp.") + tag, s, in, out, U3{0, 0, 0}, n, U3Plus());
 }
 // device-only exclusive scan of u32 on stream s (no read-back; tmp sized on first use)
 static void dev_scan_u32(rs_engine *E, const uint32_t *in, uint32_t *out, uint64_t n, hipStream_t s, const char *tag) {
-  if (!n) return;
-  size_t tb = 0;
-  HC(rocprim::exclusive_scan(nullptr, tb, in, out, (uint32_t)0, (size_t)n, rocprim::plus<uint32_t>(), s));
-  void *tmp = E->A.get<uint8_t>(std::string("dscan.tmp.") + tag, tb);
-  HC(rocprim::exclusive_scan(tmp, tb, in, out, (uint32_t)0, (size_t)n, rocprim::plus<uint32_t>(), s));
+  excl_scan(E->A, std::string("dscan.tmp.") + tag, s, in, out, (uint32_t)0, n, rocprim::plus<uint32_t>());
 }
 
 template <class K>
@@ -1773,9 +1666,7 @@ static GiantArgs giant_buffers(rs_engine *E, uint64_t n) {
   size_t tb = 0;  // the sorts' and scans' temporaries at their final size
   HC(rocprim::radix_sort_pairs(nullptr, tb, G.rkey, G.rkey2, G.rval, G.rval2, (size_t)n, 0, 64, E->stg));
   (void)A.get<uint8_t>("sort.tmp.gi", tb);
-  tb = 0;
-  HC(rocprim::exclusive_scan(nullptr, tb, G.c_nsub, G.c_dsub, (uint32_t)0, (size_t)n, rocprim::plus<uint32_t>(), E->stg));
-  (void)A.get<uint8_t>("dscan.tmp.gi", tb);
+  excl_scan(A, "dscan.tmp.gi", E->stg, (const uint32_t *)G.c_nsub, G.c_dsub, (uint32_t)0, n, rocprim::plus<uint32_t>(), true);
   return G;
 }
 // The giant path of head cluster c (position ci in the head list) on E->stg: components, the
@@ -2864,6 +2755,62 @@ CpuNear::CpuNear(const rs_engine *E) {
   if (CPU_COUNT(&want) == 0 || CPU_EQUAL(&want, &old)) return;
   set = pthread_setaffinity_np(pthread_self(), sizeof want, &want) == 0;
 }
+
+// The bracket of an engine call (the caller has checked its arguments for null): the GPU's CPUs, the
+// device, with `join` no D2H of an earlier result still on the copy stream or reading the engine's
+// buffers, then the body -- void, or an int for a call that can end in another call's code.  A failed call
+// leaves nothing queued on the two streams such a call uses, and its message in rs_last_error.
+extern "C++" template <class F>
+static int engine_call(rs_engine *E, bool join, F &&f) {
+  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (threads the call starts inherit it)
+  try {
+    HC(hipSetDevice(E->device));
+    if (join) snap_join(E);
+    if constexpr (std::is_void<decltype(f())>::value) {
+      f();
+      return RS_OK;
+    } else {
+      return f();
+    }
+  } catch (const RsError &e) {
+    (void)hipStreamSynchronize(E->stc);
+    (void)hipStreamSynchronize(E->st);
+    set_error(e.what());
+    return e.code;
+  } catch (const std::exception &e) {
+    (void)hipStreamSynchronize(E->stc);
+    (void)hipStreamSynchronize(E->st);
+    set_error(e.what());
+    return RS_E_INTERNAL;
+  }
+}
+// The bracket of a one-shot: an engine on `device` for the one call f(E)
+extern "C++" template <class F>
+static int one_shot(int device, F &&f) {
+  rs_engine *E = nullptr;
+  int rc = rs_engine_create(device, &E);
+  if (rc) return rc;
+  rc = engine_call(E, false, [&] { return f(E); });
+  rs_engine_destroy(E);
+  return rc;
+}
+// malloc'ed arrays, as rs_read_r1cs_o0's and rs_engine_fetch's (rs_input_free, rs_output_free)
+static void *malloc_buf(int, size_t bytes) {
+  void *p = malloc(bytes ? bytes : 1);
+  if (!p) throw std::bad_alloc();
+  return p;
+}
+// A one-shot that makes an rs_input: f(E, o) fills the calloc'ed *o; a failed call frees what it holds so far
+extern "C++" template <class F>
+static int one_shot_input(int device, rs_input **in, F &&f) {
+  *in = nullptr;
+  rs_input *o = (rs_input *)calloc(1, sizeof(rs_input));
+  if (!o) { set_error("out of memory"); return RS_E_INTERNAL; }
+  const int rc = one_shot(device, [&](rs_engine *E) { f(E, o); });
+  if (rc) rs_input_free(o);
+  else *in = o;
+  return rc;
+}
 }  // namespace rs
 
 int rs_engine_create(int device, rs_engine **eng) {
@@ -3258,27 +3205,17 @@ static void fetch_result_shared(rs_engine *E, rs_output *o, bool own_log) {
 }  // namespace rs
 
 int rs_engine_fetch(rs_engine *E, rs_output **out) {
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return
-  try {
-    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
+  return engine_call(E, false, [&] {
+    if (!E->have_result) throw RsError(RS_E_INVALID, "no result");
     rs_output *o = (rs_output *)calloc(1, sizeof(rs_output));
     try {
-      fetch_result(E, o, [](int, size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (!p) throw std::bad_alloc(); return p; }, true,
-                   false);
+      fetch_result(E, o, malloc_buf, true, false);
     } catch (...) {
       rs_output_free(o);
       throw;
     }
     *out = o;
-    return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 int rs_engine_simplify(rs_engine *E, const rs_input *in, const rs_flags *fl, const rs_output **out) {
@@ -3324,10 +3261,8 @@ int rs_engine_simplify(rs_engine *E, const rs_input *in, const rs_flags *fl, con
 // rs_write_r1cs on the fetched output): the constraint section is built on the device (writer.hpp)
 // and streamed to the file through two pinned staging buffers; the small sections follow.  o0_r1cs (optional): custom-gate sections as rs_write_r1cs_gates.
 int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return
-  try {
-    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
+  return engine_call(E, false, [&]() -> int {
+    if (!E->have_result) throw RsError(RS_E_INVALID, "no result");
     const double t0 = now_ms();
     Arena &A = E->A;
     hipStream_t st = E->st;
@@ -3420,39 +3355,13 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
       if (E->n_wires) tail.insert(tail.end(), (const uint8_t *)hw2l.data(), (const uint8_t *)(hw2l.data() + E->n_wires));
       if (with_gates) tail.insert(tail.end(), gates.begin(), gates.end());
     }
-    ImageOut io;
-    io.prepare(E, dev_bytes);
-    struct Fd {
-      int fd;
-      ~Fd() {
-        if (fd >= 0) close(fd);
-      }
-    } file{open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644)};
-    if (file.fd < 0) throw RsError(RS_E_INVALID, std::string("cannot write ") + path);
-    const int fd = file.fd;
-    std::atomic<bool> io_err{false};
-    const uint64_t img_off = head.size(), fsize = img_off + dev_bytes + tail.size();
-    // the file's blocks up front (a fresh 0.92 GB file: 10.0 -> 11.4 GB/s from host memory on the GPU box's
-    // /tmp, tools/writer_bench.py); a file system without fallocate gets the size by ftruncate
-    if (posix_fallocate(fd, 0, (off_t)fsize) != 0 && ftruncate(fd, (off_t)fsize) != 0) io_err = true;
-    if (!pwrite_all(fd, head.data(), head.size(), 0)) io_err = true;
-    if (!pwrite_all(fd, tail.data(), tail.size(), img_off + dev_bytes)) io_err = true;
-    io.run(st, fd, (const uint8_t *)img, dev_bytes, img_off, io_err);
-    file.fd = -1;
-    if (close(fd) != 0) io_err = true;
-    if (io_err) throw RsError(RS_E_INVALID, "write error");
+    write_image_file(E, path, {head.data(), head.size()}, {tail.data(), tail.size()}, img, dev_bytes, st);
     if (g_prof_env)
       fprintf(stderr, "[rs-prof] write_r1cs: device image %.1f MB built in %.2f ms, D2H + %d writers %.2f ms\n", dev_bytes / 1e6,
               t_built - t0, ImageOut::kThreads, now_ms() - t_built);
     E->stats.write_ms = now_ms() - t0;
     return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 // The last result's label_to_wire (resident: fin.l2w) applied to the --O0 .sym on the device
@@ -3460,11 +3369,8 @@ int rs_engine_write_r1cs(rs_engine *E, const char *path, const char *o0_r1cs) {
 // rs_engine_write_r1cs, from this rank's own complete copy, no collective.
 int rs_engine_write_sym(rs_engine *E, const char *o0_sym, const char *path) {
   if (!E || !o0_sym || !path) { set_error("rs_engine_write_sym: null argument"); return RS_E_INVALID; }
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (the reader and writer threads inherit it)
-  try {
-    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
-    snap_join(E);  // no D2H of the result still uses the copy stream
+  return engine_call(E, true, [&]() -> int {
+    if (!E->have_result) throw RsError(RS_E_INVALID, "no result");
     const int32_t *l2w = E->A.get<int32_t>("fin.l2w", 1);
     if (env_flag("RS_WRITER_HOST")) {  // the host writer over the fetched label_to_wire (same bytes)
       const double t0 = now_ms();
@@ -3481,13 +3387,7 @@ int rs_engine_write_sym(rs_engine *E, const char *o0_sym, const char *path) {
     }
     write_sym_device(E, o0_sym, path, l2w, E->S);
     return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 // The one-shot: out->label_to_wire goes to the device, nothing else of `out` is read.
@@ -3496,24 +3396,11 @@ int rs_write_sym_device(int device, const char *o0_sym, const char *path, const 
     set_error("rs_write_sym_device: null argument");
     return RS_E_INVALID;
   }
-  rs_engine *E = nullptr;
-  int rc = rs_engine_create(device, &E);
-  if (rc) return rc;
-  try {
-    HC(hipSetDevice(E->device));
+  return one_shot(device, [&](rs_engine *E) {
     int32_t *l2w = E->SA.get<int32_t>("sym.l2w", out->n_labels);
     h2d(E, l2w, out->label_to_wire, 4 * out->n_labels);
     write_sym_device(E, o0_sym, path, l2w, out->n_labels);
-    rc = RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    rc = e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    rc = RS_E_INTERNAL;
-  }
-  rs_engine_destroy(E);
-  return rc;
+  });
 }
 
 // ---- the --json and --simplification_substitution files on the device (json_write.hpp)
@@ -3539,11 +3426,8 @@ static int json_via_host(rs_engine *E, const char *path, bool log) {
 // sharded engine: like rs_engine_write_r1cs, from this rank's own complete copy, no collective.
 int rs_engine_write_constraints_json(rs_engine *E, const char *path) {
   if (!E || !path) { set_error("rs_engine_write_constraints_json: null argument"); return RS_E_INVALID; }
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (the writer threads inherit it)
-  try {
-    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
-    snap_join(E);  // no D2H of the result still uses the copy stream
+  return engine_call(E, true, [&]() -> int {
+    if (!E->have_result) throw RsError(RS_E_INVALID, "no result");
     if (env_flag("RS_WRITER_HOST")) return json_via_host(E, path, false);
     const double t0 = now_ms();
     ensure_csr(E);  // (before the writer's own buffers: they live in another arena and move nothing of the result)
@@ -3561,24 +3445,15 @@ int rs_engine_write_constraints_json(rs_engine *E, const char *path) {
     s.n_labels = E->S;
     write_json_device(E, s, path, t0, t0);
     return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 // The last run's substitution log (the engine's host vectors) as <prefix>_substitutions.json: up through
 // the pinned staging pool on the copy stream, then the formatter.
 int rs_engine_write_substitution_json(rs_engine *E, const char *path) {
   if (!E || !path) { set_error("rs_engine_write_substitution_json: null argument"); return RS_E_INVALID; }
-  CpuNear cpu_near_(E);
-  try {
-    if (!E->have_result) { set_error("no result"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
-    snap_join(E);
+  return engine_call(E, true, [&]() -> int {
+    if (!E->have_result) throw RsError(RS_E_INVALID, "no result");
     if (env_flag("RS_WRITER_HOST")) return json_via_host(E, path, true);
     const double t0 = now_ms();
     JsonSrc s;
@@ -3593,25 +3468,11 @@ int rs_engine_write_substitution_json(rs_engine *E, const char *path) {
       uint32_t *from = A.get<uint32_t>("json.log.from", n), *key = A.get<uint32_t>("json.log.key", nnz);
       uint64_t *ptr = A.get<uint64_t>("json.log.ptr", n + 1), *val = A.get<uint64_t>("json.log.val", 4 * nnz);
       const uint64_t all = 4 * n + 8 * (n + 1) + 36 * nnz;
-      const uint64_t stage = std::min<uint64_t>(kRrStage, (all + 4095) & ~4095ull);
-      uint8_t *pool = (uint8_t *)pin_get(E, kPinStage, kRrBufs * stage);
-      struct Events {
-        hipEvent_t e[kRrBufs] = {};
-        ~Events() {
-          for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-        }
-      } evs;
-      for (hipEvent_t &x : evs.e) HC(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-      struct Drain {  // the pool is free again on every way out
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-      } drain{E->stc};
-      uint64_t seq = 0;
-      json_stage_up(E, pool, stage, evs.e, seq, from, E->log_from.data(), 4 * n);
-      json_stage_up(E, pool, stage, evs.e, seq, ptr, E->log_ptr.data(), 8 * (n + 1));
-      json_stage_up(E, pool, stage, evs.e, seq, key, E->log_key.data(), 4 * nnz);
-      json_stage_up(E, pool, stage, evs.e, seq, val, E->log_val.data(), 32 * nnz);
+      StageIn up(E, (all + 4095) & ~4095ull);
+      up.send(from, E->log_from.data(), 4 * n);
+      up.send(ptr, E->log_ptr.data(), 8 * (n + 1));
+      up.send(key, E->log_key.data(), 4 * nnz);
+      up.send(val, E->log_val.data(), 32 * nnz);
       HC(hipStreamSynchronize(E->stc));
       t_in = now_ms();
       s.from = from;
@@ -3622,13 +3483,7 @@ int rs_engine_write_substitution_json(rs_engine *E, const char *path) {
     }
     write_json_device(E, s, path, t0, t_in);
     return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 int rs_engine_json_stats(rs_engine *E, rs_json_stats *st) {
@@ -3644,11 +3499,7 @@ int rs_write_constraints_json_device(int device, const char *path, const rs_outp
     set_error("rs_write_constraints_json_device: null argument");
     return RS_E_INVALID;
   }
-  rs_engine *E = nullptr;
-  int rc = rs_engine_create(device, &E);
-  if (rc) return rc;
-  try {
-    HC(hipSetDevice(E->device));
+  return one_shot(device, [&](rs_engine *E) {
     const double t0 = now_ms();
     const rs_lc *L[3] = {&out->a, &out->b, &out->c};
     const uint32_t *len[3] = {out->a_len, out->b_len, out->c_len};
@@ -3667,16 +3518,7 @@ int rs_write_constraints_json_device(int device, const char *path, const rs_outp
     s.l2w = l2w;
     s.n_labels = out->n_labels;
     write_json_device(E, s, path, t0, now_ms());
-    rc = RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    rc = e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    rc = RS_E_INTERNAL;
-  }
-  rs_engine_destroy(E);
-  return rc;
+  });
 }
 
 int rs_write_substitution_json_device(int device, const char *path, const rs_output *out) {
@@ -3684,11 +3526,7 @@ int rs_write_substitution_json_device(int device, const char *path, const rs_out
     set_error("rs_write_substitution_json_device: null argument");
     return RS_E_INVALID;
   }
-  rs_engine *E = nullptr;
-  int rc = rs_engine_create(device, &E);
-  if (rc) return rc;
-  try {
-    HC(hipSetDevice(E->device));
+  return one_shot(device, [&](rs_engine *E) {
     const double t0 = now_ms();
     JsonHostPart hp;
     JsonSrc s;
@@ -3703,46 +3541,13 @@ int rs_write_substitution_json_device(int device, const char *path, const rs_out
     }
     HC(hipStreamSynchronize(E->st));
     write_json_device(E, s, path, t0, now_ms());
-    rc = RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    rc = e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    rc = RS_E_INTERNAL;
-  }
-  rs_engine_destroy(E);
-  return rc;
+  });
 }
 
 // ---- the witness on the device (witness.hpp)
-namespace rs {
-// the bracket of a witness call: nothing of it may still be queued when it fails
-extern "C++" template <class F>
-static int wit_call(rs_engine *E, F &&f) {
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return
-  try {
-    HC(hipSetDevice(E->device));
-    snap_join(E);  // no D2H of a result still uses the copy stream
-    f();
-    return RS_OK;
-  } catch (const RsError &e) {
-    (void)hipStreamSynchronize(E->stc);
-    (void)hipStreamSynchronize(E->st);
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    (void)hipStreamSynchronize(E->stc);
-    (void)hipStreamSynchronize(E->st);
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
-}
-}  // namespace rs
-
 int rs_engine_load_witness(rs_engine *E, const rs_witness *w) {
   if (!E || !w || (w->n && !w->val)) { set_error("rs_engine_load_witness: null argument"); return RS_E_INVALID; }
-  return wit_call(E, [&] {
+  return engine_call(E, true, [&] {
     uint64_t p[4];
     if (!wtns::witness_prime(w, p)) throw RsError(RS_E_INVALID, "rs_engine_load_witness: bad prime or field size");
     if (w->n == 0 || w->n > 0x7fffffffull) throw RsError(RS_E_INVALID, "rs_engine_load_witness: the witness needs 1 .. 2^31 - 1 values");
@@ -3756,26 +3561,26 @@ int rs_engine_load_witness(rs_engine *E, const rs_witness *w) {
 
 int rs_engine_load_wtns(rs_engine *E, const char *path) {
   if (!E || !path) { set_error("rs_engine_load_wtns: null argument"); return RS_E_INVALID; }
-  return wit_call(E, [&] {
-    wtns::Fd f{-1};
+  return engine_call(E, true, [&] {
+    Fd f;
     wtns::Head H;
     if (!wtns::open_head(path, f, H)) throw RsError(RS_E_INVALID, rs_last_error());
     if (H.n == 0 || H.n > 0x7fffffffull) throw RsError(RS_E_INVALID, "rs_engine_load_wtns: the witness needs 1 .. 2^31 - 1 values");
     const int fd = f.fd;
     const uint64_t off2 = H.off2, n8 = H.n8;
     wit_upload(E, H.n, H.n8, H.n8, H.prime, H.prime_id,
-               [fd, off2, n8](uint8_t *dst, uint64_t i0, uint64_t cnt) { return wtns::pread_all(fd, dst, cnt * n8, off2 + i0 * n8); });
+               [fd, off2, n8](uint8_t *dst, uint64_t i0, uint64_t cnt) { return pread_all(fd, dst, cnt * n8, off2 + i0 * n8); });
   });
 }
 
 int rs_engine_check_witness(rs_engine *E, const rs_input *in, uint32_t what, rs_witness_report *rep) {
   if (!E || !rep) { set_error("rs_engine_check_witness: null argument"); return RS_E_INVALID; }
-  return wit_call(E, [&] { check_witness_device(E, in, what, rep); });
+  return engine_call(E, true, [&] { check_witness_device(E, in, what, rep); });
 }
 
 int rs_engine_write_wtns(rs_engine *E, const char *path) {
   if (!E || !path) { set_error("rs_engine_write_wtns: null argument"); return RS_E_INVALID; }
-  return wit_call(E, [&] { write_wtns_device(E, path); });
+  return engine_call(E, true, [&] { write_wtns_device(E, path); });
 }
 
 void *rs_host_alloc(uint64_t bytes) {
@@ -3820,37 +3625,19 @@ int rs_comm_unique_id(uint8_t id[RS_COMM_ID_BYTES]) {
 }
 
 int rs_engine_join_rccl(rs_engine *E, int world, int rank, const uint8_t id[RS_COMM_ID_BYTES]) {
-  try {
-    if (world < 1 || world > 255 || rank < 0 || rank >= world) { set_error("bad world/rank"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
+  if (world < 1 || world > 255 || rank < 0 || rank >= world) { set_error("bad world/rank"); return RS_E_INVALID; }
+  return engine_call(E, false, [&] {
     ncclUniqueId u;
     memcpy(&u, id, RS_COMM_ID_BYTES);
     ncclComm_t c = nullptr;
     NC(ncclCommInitRank(&c, world, u, rank));
     E->comm.reset(new RcclComm(c, rank, world));
-    return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 int rs_engine_join_host(rs_engine *E, int world, int rank, const char *tag) {
-  try {
-    if (!E || !tag || world < 1 || world > 255 || rank < 0 || rank >= world) { set_error("bad world/rank/tag"); return RS_E_INVALID; }
-    HC(hipSetDevice(E->device));
-    E->comm.reset(new HostComm(world, rank, tag));
-    return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  if (!E || !tag || world < 1 || world > 255 || rank < 0 || rank >= world) { set_error("bad world/rank/tag"); return RS_E_INVALID; }
+  return engine_call(E, false, [&] { E->comm.reset(new HostComm(world, rank, tag)); });
 }
 
 int rs_engine_inject_fault(rs_engine *E, int where) {
@@ -3924,103 +3711,35 @@ int rs_simplify_multi(const rs_input *in, const rs_flags *fl, int n_dev, const i
 
 int rs_flatten_dag(int device, const rs_dag *dag, rs_input **in) {
   if (!dag || !in) { set_error("rs_flatten_dag: null argument"); return RS_E_INVALID; }
-  *in = nullptr;
-  rs_engine *E = nullptr;
-  int rc = rs_engine_create(device, &E);
-  if (rc) return rc;
-  rs_input *o = (rs_input *)calloc(1, sizeof(rs_input));
-  try {
-    HC(hipSetDevice(E->device));
-    flatten_dag(E, dag, o, [](int, size_t bytes) {  // malloc'ed like rs_read_r1cs_o0's (rs_input_free)
-      void *p = malloc(bytes ? bytes : 1);
-      if (!p) throw std::bad_alloc();
-      return p;
-    });
-    *in = o;
-    o = nullptr;
-    rc = RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    rc = e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    rc = RS_E_INTERNAL;
-  }
-  if (o) rs_input_free(o);  // a failed call: the arrays made so far (calloc'ed struct: NULL elsewhere)
-  rs_engine_destroy(E);
-  return rc;
+  return one_shot_input(device, in, [&](rs_engine *E, rs_input *o) { flatten_dag(E, dag, o, malloc_buf); });
 }
 
 int rs_engine_flatten_dag(rs_engine *E, const rs_dag *dag, const rs_input **in) {
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return
   if (!E || !dag || !in) { set_error("rs_engine_flatten_dag: null argument"); return RS_E_INVALID; }
   *in = nullptr;
-  try {
-    HC(hipSetDevice(E->device));
-    snap_join(E);  // no D2H of an earlier result still reads the engine's buffers
+  return engine_call(E, true, [&] {
     E->flat_view = rs_input{};
     flatten_dag(E, dag, &E->flat_view, [E](int slot, size_t bytes) { return pin_get(E, kPinFlat + slot, bytes); });
     *in = &E->flat_view;
-    return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 // The device --O0 reader (r1cs_read.hpp).  The one-shot: malloc'ed arrays like rs_read_r1cs_o0's.
 int rs_read_r1cs_o0_device(int device, const char *path, rs_input **in) {
   if (!path || !in) { set_error("rs_read_r1cs_o0_device: null argument"); return RS_E_INVALID; }
-  *in = nullptr;
-  rs_engine *E = nullptr;
-  int rc = rs_engine_create(device, &E);
-  if (rc) return rc;
-  rs_input *o = (rs_input *)calloc(1, sizeof(rs_input));
-  try {
-    HC(hipSetDevice(E->device));
-    read_r1cs_device(E, path, o, [](int, size_t bytes) {
-      void *p = malloc(bytes ? bytes : 1);
-      if (!p) throw std::bad_alloc();
-      return p;
-    });
-    *in = o;
-    o = nullptr;
-    rc = RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    rc = e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    rc = RS_E_INTERNAL;
-  }
-  if (o) rs_input_free(o);  // a failed call: the arrays made so far (calloc'ed struct: NULL elsewhere)
-  rs_engine_destroy(E);
-  return rc;
+  return one_shot_input(device, in, [&](rs_engine *E, rs_input *o) { read_r1cs_device(E, path, o, malloc_buf); });
 }
 
 // On a persistent engine, into the page-locked buffers rs_engine_flatten_dag's result uses too
 // (flat_view, pin[kPinFlat..]): *in is valid until the next read or flatten on `eng`.
 int rs_engine_read_r1cs_o0(rs_engine *E, const char *path, const rs_input **in) {
   if (!E || !path || !in) { set_error("rs_engine_read_r1cs_o0: null argument"); return RS_E_INVALID; }
-  CpuNear cpu_near_(E);  // the caller's affinity is restored on return (the reader thread inherits it)
   *in = nullptr;
-  try {
-    HC(hipSetDevice(E->device));
-    snap_join(E);  // no D2H of an earlier result still reads the engine's buffers
+  return engine_call(E, true, [&] {
     E->flat_view = rs_input{};
     read_r1cs_device(E, path, &E->flat_view, [E](int slot, size_t bytes) { return pin_get(E, kPinFlat + slot, bytes); });
     *in = &E->flat_view;
-    return RS_OK;
-  } catch (const RsError &e) {
-    set_error(e.what());
-    return e.code;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return RS_E_INTERNAL;
-  }
+  });
 }
 
 int rs_simplify(const rs_input *in, const rs_flags *fl, rs_output **out) {

@@ -352,11 +352,7 @@ static void flatten_dag(rs_engine *E, const rs_dag *D, rs_input *in, const std::
   A.cnt = E->A.get<FlCnt>("fl.cnt", n_inst);
   A.pre = E->A.get<FlCnt>("fl.pre", n_inst);
   launch(st, k_fl_counts, n_inst, A, d_mcount);
-  size_t tb = 0;
-  FlCnt zero{};
-  HC(rocprim::exclusive_scan(nullptr, tb, A.cnt, A.pre, zero, (size_t)n_inst, FlCntPlus(), st));
-  void *tmp = E->A.get<uint8_t>("fl.scan", tb);
-  HC(rocprim::exclusive_scan(tmp, tb, A.cnt, A.pre, zero, (size_t)n_inst, FlCntPlus(), st));
+  excl_scan(E->A, "fl.scan", st, (const FlCnt *)A.cnt, A.pre, FlCnt{}, n_inst, FlCntPlus());
   FlCnt last_c, last_p, tot;
   HC(hipMemcpyAsync(&last_c, A.cnt + n_inst - 1, sizeof(FlCnt), hipMemcpyDeviceToHost, st));
   HC(hipMemcpyAsync(&last_p, A.pre + n_inst - 1, sizeof(FlCnt), hipMemcpyDeviceToHost, st));

@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include <unistd.h>
+
 #include "../../include/rs_simplify.h"
 
 namespace rs {
@@ -88,6 +90,42 @@ struct R1csO0Head {
 bool r1cs_o0_small(const uint8_t *s1, uint64_t size1, const uint8_t *s4, uint64_t size4, const uint8_t *s5, uint64_t size5,
                    R1csO0Head &H);
 bool r1cs_o0_open(const char *path, int *fd, R1csSections &S, R1csO0Head &H);
+
+// An open file, closed on every way out of its scope (release(): the caller closes it and sees the verdict)
+struct Fd {
+  int fd = -1;
+  ~Fd() {
+    if (fd >= 0) close(fd);
+  }
+  int release() {
+    const int f = fd;
+    fd = -1;
+    return f;
+  }
+};
+// All n bytes at `off`, over short reads / writes; false: an error, or the file ends first
+inline bool pread_all(int fd, void *dst, uint64_t n, uint64_t off) {
+  uint8_t *d = (uint8_t *)dst;
+  while (n) {
+    const ssize_t g = pread(fd, d, n, (off_t)off);
+    if (g <= 0) return false;
+    d += g;
+    n -= (uint64_t)g;
+    off += (uint64_t)g;
+  }
+  return true;
+}
+inline bool pwrite_all(int fd, const void *src, uint64_t n, uint64_t off) {
+  const uint8_t *p = (const uint8_t *)src;
+  while (n) {
+    const ssize_t w = pwrite(fd, p, n, (off_t)off);
+    if (w <= 0) return false;
+    p += w;
+    n -= (uint64_t)w;
+    off += (uint64_t)w;
+  }
+  return true;
+}
 
 inline void free_lc(rs_lc &lc) {
   free(lc.ptr);

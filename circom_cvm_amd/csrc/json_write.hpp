@@ -33,7 +33,7 @@
 // An entry that straddles a chunk border is converted by both neighbours; every image byte has exactly
 // one writer and nothing is atomic.  A row of 100 k entries is simply many chunks.
 #pragma once
-// (included by engine.hip inside namespace rs, after its scan helpers and ImageOut)
+// (included by engine.hip inside namespace rs, after its scan helpers and stage_io.hpp)
 
 constexpr uint64_t kJsonChunk = 16384, kJsonChunkMin = 64, kJsonChunkMax = 65536;  // a power of two
 constexpr int kJsonErrRemoved = 1, kJsonErrOrder = 2;
@@ -307,10 +307,7 @@ struct JsonSrc {
 };
 
 static void json_scan(rs_engine *E, const uint64_t *in, uint64_t *out, uint64_t n) {
-  size_t tb = 0;
-  HC(rocprim::exclusive_scan(nullptr, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E->st));
-  void *tmp = E->SA.get<uint8_t>("json.scan", tb);
-  HC(rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), E->st));
+  excl_scan(E->SA, "json.scan", E->st, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>());
 }
 
 // The rows of `s` (device, their producers on the main stream or done) as the file at `path`.  t0: when the
@@ -322,7 +319,6 @@ static void write_json_device(rs_engine *E, const JsonSrc &s, const char *path, 
   while (chunk & (chunk - 1)) chunk &= chunk - 1;  // a power of two (rounded down)
   const bool log = s.nparts == 1;
   const char *head = log ? "{" : "{\n\"constraints\": [", *tail = log ? "\n}" : "\n]\n}";
-  const uint64_t n_head = strlen(head), n_tail = strlen(tail);
   JsonGeom g{};
   g.n = s.n;
   g.nparts = (uint32_t)s.nparts;
@@ -331,14 +327,7 @@ static void write_json_device(rs_engine *E, const JsonSrc &s, const char *path, 
   g.l2w = s.l2w;
   g.n_labels = s.n_labels;
   g.C = (uint32_t)chunk;
-  struct Events {
-    hipEvent_t e[6] = {};  // around pass 1, the scans, pass 2
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  for (hipEvent_t &x : evs.e) HC(hipEventCreate(&x));
+  Events<6> evs(hipEventDefault);  // around pass 1, the scans, pass 2
   uint8_t *img = nullptr;
   if (s.n) {
     const char *nm[3] = {"json.a", "json.b", "json.c"};
@@ -391,31 +380,12 @@ static void write_json_device(rs_engine *E, const JsonSrc &s, const char *path, 
     HC(hipEventRecord(evs.e[5], st));
   }
   const double t_valid = now_ms();
-  // ---- the file (its blocks up front, while k_json_emit runs), then the image through ImageOut
-  ImageOut io;
-  io.prepare(E, g.total);
-  struct Fd {
-    int fd;
-    ~Fd() {
-      if (fd >= 0) close(fd);
-    }
-  } dst{open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644)};
-  if (dst.fd < 0) throw RsError(RS_E_INVALID, std::string("cannot write ") + path);
-  std::atomic<bool> io_err{false};
-  const uint64_t fsize = n_head + g.total + n_tail;
-  if (posix_fallocate(dst.fd, 0, (off_t)fsize) != 0 && ftruncate(dst.fd, (off_t)fsize) != 0) io_err = true;
-  if (!pwrite_all(dst.fd, (const uint8_t *)head, n_head, 0)) io_err = true;
-  if (!pwrite_all(dst.fd, (const uint8_t *)tail, n_tail, n_head + g.total)) io_err = true;
+  // ---- the file (its blocks up front, while k_json_emit runs), then the image
   float ms[3] = {0, 0, 0};
-  if (s.n) {
+  write_image_file(E, path, {head, strlen(head)}, {tail, strlen(tail)}, img, g.total, st, [&] {
     HC(hipEventSynchronize(evs.e[5]));
     for (int k = 0; k < 3; ++k) HC(hipEventElapsedTime(&ms[k], evs.e[2 * k], evs.e[2 * k + 1]));
-    io.run(st, dst.fd, img, g.total, n_head, io_err);
-  }
-  const int fd = dst.fd;
-  dst.fd = -1;
-  if (close(fd) != 0) io_err = true;
-  if (io_err) throw RsError(RS_E_INVALID, "write error");
+  });
   const double t_end = now_ms();
   rs_json_stats &js = E->jstats;
   js.write_ms = t_end - t0;
@@ -494,17 +464,5 @@ static void json_upload_part(rs_engine *E, const JsonHostPart &hp, uint64_t n, c
   s.col[q] = col;
   s.val[q] = val;
   s.nnz[q] = hp.nnz;
-}
-
-// The engine's log (host vectors) to the device through the pinned staging pool on the copy stream
-static void json_stage_up(rs_engine *E, uint8_t *pool, uint64_t stage, hipEvent_t *ev, uint64_t &seq, void *dst, const void *src, uint64_t bytes) {
-  for (uint64_t off = 0; off < bytes; off += stage, ++seq) {
-    const int b = (int)(seq % kRrBufs);
-    if (seq >= (uint64_t)kRrBufs) HC(hipEventSynchronize(ev[b]));
-    const uint64_t len = std::min(stage, bytes - off);
-    memcpy(pool + (uint64_t)b * stage, (const uint8_t *)src + off, len);
-    HC(hipMemcpyAsync((uint8_t *)dst + off, pool + (uint64_t)b * stage, len, hipMemcpyHostToDevice, E->stc));
-    HC(hipEventRecord(ev[b], E->stc));
-  }
 }
 #endif  // __HIPCC__

@@ -3,8 +3,8 @@
 // rs_read_r1cs_o0 (r1cs_io.cpp), which classifies like dag/src/map_to_constraint_list.rs:12-44.
 //
 // The host parses the section table and the small sections (header, custom gates) through preads
-// (r1cs_o0_open) and never looks at the constraint section: a reader thread streams it through
-// pinned staging buffers to the device, where it is an array of E = size / 4 four-byte slots (every
+// (r1cs_o0_open) and never looks at the constraint section: it is streamed through the pinned
+// staging buffers (StageIn, stage_io.hpp) to the device, where it is an array of E = size / 4 four-byte slots (every
 // size in the format is a multiple of 4, so every linear combination -- `u32 n`, then n x (u32
 // signal, fs bytes) -- starts at a slot).  Where the LCs start is sequentially dependent: LC j + 1
 // starts where LC j ends.  The device finds the starts in parallel by treating EVERY slot i as a
@@ -316,22 +316,13 @@ __global__ void __launch_bounds__(256) k_r1cs_emit(const uint32_t *sec, const ui
 }
 
 // buf(slot, bytes): as flatten_dag's -- slots 3q, 3q + 1, 3q + 2 for block q's ptr, col, val, 18 for
-// forbidden.  The staging pool: kRrBufs pinned buffers of kRrStage bytes (pin slot kPinStage), filled
-// by a reader thread (pread) and sent on the copy stream; a buffer is refilled once its copy is done.
-constexpr uint64_t kRrStage = 32ull << 20;
-constexpr int kRrBufs = 4;
-
+// forbidden.  The section goes up through StageIn (stage_io.hpp), a pread a piece, on the calling thread.
 static void read_r1cs_device(rs_engine *E, const char *path, rs_input *in, const std::function<void *(int, size_t)> &buf) {
   hipStream_t st = E->st;
   const double t0 = now_ms();
   R1csSections S;
   R1csO0Head H;
-  struct Fd {
-    int fd = -1;
-    ~Fd() {
-      if (fd >= 0) close(fd);
-    }
-  } file;
+  Fd file;
   if (!r1cs_o0_open(path, &file.fd, S, H)) throw RsError(RS_E_INVALID, rs_last_error());
   const uint64_t n_cons = H.n_cons, n_lc = 3 * n_cons;
   RrGeom g{};
@@ -350,51 +341,8 @@ static void read_r1cs_device(rs_engine *E, const char *path, rs_input *in, const
   RrOut O{};
   double t_up = t0, t_k = t0;
   if (n_cons) {
-    // ---- section 2 -> device, untouched: pread into the pinned pool on a reader thread, H2D on the copy stream
+    // ---- the tables (an arena buffer that grows is a hipFree, which waits for the device: before the upload)
     uint32_t *sec = A.get<uint32_t>("rr.sec", g.E);  // (hipMalloc: aligned)
-    const uint64_t bytes = 4 * g.E, nst = (bytes + kRrStage - 1) / kRrStage;
-    uint8_t *pool = (uint8_t *)pin_get(E, kPinStage, kRrBufs * std::min<uint64_t>(kRrStage, bytes));
-    const uint64_t stage = std::min<uint64_t>(kRrStage, bytes);
-    struct Events {
-      hipEvent_t e[kRrBufs] = {};
-      ~Events() {
-        for (hipEvent_t x : e)
-          if (x) (void)hipEventDestroy(x);
-      }
-    } evs;
-    for (auto &e : evs.e) HC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    int io_rc = 0;  // the thread's verdict (read after the join): 1 file, 2 HIP
-    const int fd = file.fd, device = E->device;
-    const uint64_t off2 = S.off[2];
-    hipStream_t stc = E->stc;
-    struct Joined {
-      std::thread th;
-      ~Joined() {
-        if (th.joinable()) th.join();
-      }
-    } reader;
-    reader.th = std::thread([&, fd, device, off2, stc]() {
-      if (hipSetDevice(device) != hipSuccess) { io_rc = 2; return; }
-      for (uint64_t i = 0; i < nst; ++i) {
-        const int b = (int)(i % kRrBufs);
-        if (i >= (uint64_t)kRrBufs && hipEventSynchronize(evs.e[b]) != hipSuccess) { io_rc = 2; break; }
-        const uint64_t off = i * stage, len = std::min(stage, bytes - off);
-        uint8_t *dst = pool + (uint64_t)b * stage;
-        for (uint64_t got = 0; got < len;) {
-          const ssize_t k = pread(fd, dst + got, len - got, (off_t)(off2 + off + got));
-          if (k <= 0) { io_rc = 1; break; }
-          got += (uint64_t)k;
-        }
-        if (io_rc) break;
-        if (hipMemcpyAsync((uint8_t *)sec + off, dst, len, hipMemcpyHostToDevice, stc) != hipSuccess ||
-            hipEventRecord(evs.e[b], stc) != hipSuccess) {
-          io_rc = 2;
-          break;
-        }
-      }
-      if (hipStreamSynchronize(stc) != hipSuccess && !io_rc) io_rc = 2;  // the pool is free again; the section has landed
-    });
-    // meanwhile: the tables
     const uint64_t n_words = g.n_chunks * (g.C / 32);
     uint32_t *exitp = A.get<uint32_t>("rr.exit", g.E);
     uint32_t *gexit = A.get<uint32_t>("rr.gexit", g.n_groups * g.C);
@@ -409,9 +357,15 @@ static void read_r1cs_device(rs_engine *E, const char *path, rs_input *in, const
     HC(hipMemsetAsync(d_err, 0, 4, st));
     HC(hipMemsetAsync(gentry, 0xff, 4 * g.n_groups, st));
     HC(hipMemsetAsync(centry, 0xff, 4 * g.n_chunks, st));
-    reader.th.join();
-    if (io_rc == 1) throw RsError(RS_E_INVALID, std::string("cannot read r1cs file ") + path);
-    if (io_rc) throw RsError(RS_E_HIP, "rs_read_r1cs_o0_device: the upload of the constraint section failed");
+    // ---- section 2 -> device, untouched
+    {
+      const int fd = file.fd;
+      const uint64_t off2 = S.off[2];
+      StageIn up(E, 4 * g.E);
+      up.send(sec, 4 * g.E, std::string("cannot read r1cs file ") + path,
+              [fd, off2](uint8_t *dst, uint64_t off, uint64_t len) { return pread_all(fd, dst, len, off2 + off); });
+      HC(hipStreamSynchronize(E->stc));  // the section has landed
+    }
     t_up = now_ms();
     Marks mk{{}, st};  // RS_PROF: the time of every step (the stream synchronised at each mark)
     mk.mark("read_r1cs: start");
@@ -440,11 +394,7 @@ static void read_r1cs_device(rs_engine *E, const char *path, rs_input *in, const
     memcpy(P.p, H.prime, 32);
     launch(st, k_r1cs_classify, n_cons, (const uint32_t *)sec, (const uint32_t *)lc_pos, n_cons, g.W, P, cls, cnt);
     mk.mark("classify");
-    size_t tb = 0;
-    const RrCnt zero{};
-    HC(rocprim::exclusive_scan(nullptr, tb, cnt, pre, zero, (size_t)n_cons, RrCntPlus(), st));
-    void *tmp = A.get<uint8_t>("rr.scan", tb);
-    HC(rocprim::exclusive_scan(tmp, tb, cnt, pre, zero, (size_t)n_cons, RrCntPlus(), st));
+    excl_scan(A, "rr.scan", st, (const RrCnt *)cnt, pre, RrCnt{}, n_cons, RrCntPlus());
     RrCnt last_c, last_p;
     HC(hipMemcpyAsync(&last_c, cnt + n_cons - 1, sizeof(RrCnt), hipMemcpyDeviceToHost, st));
     HC(hipMemcpyAsync(&last_p, pre + n_cons - 1, sizeof(RrCnt), hipMemcpyDeviceToHost, st));

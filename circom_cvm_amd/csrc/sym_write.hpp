@@ -258,21 +258,18 @@ __global__ void __launch_bounds__(256) k_sym_emit(const uint8_t *in, SymGeom g, 
   }
 }
 
-// The --O0 .sym at o0_sym rewritten with l2w (device, n_labels entries) to path.  The input goes up like
-// the --O0 .r1cs (r1cs_read.hpp): a reader thread preads it into the pinned staging pool and sends each
-// buffer on the copy stream, followed there by k_sym_count over the buffer's chunks (a buffer is a whole
-// number of chunks; a chunk's 32 bytes of look-back landed with the buffer before).
+// The --O0 .sym at o0_sym rewritten with l2w (device, n_labels entries) to path.  The input goes up through
+// StageIn (stage_io.hpp), a pread a piece, each piece followed on the copy stream by k_sym_count over its
+// chunks (a buffer is a whole number of chunks; a chunk's 32 bytes of look-back landed with the buffer before).
+static_assert(kIoStageMin % kSymChunkMax == 0, "a staging buffer is a whole number of .sym chunks");
 static void write_sym_device(rs_engine *E, const char *o0_sym, const char *path, const int32_t *l2w, uint64_t n_labels) {
   const double t0 = now_ms();
   hipStream_t st = E->st, stc = E->stc;
-  struct Fd {
-    int fd;
-    ~Fd() {
-      if (fd >= 0) close(fd);
-    }
-  } src{open(o0_sym, O_RDONLY)}, dst{-1};
+  const std::string cannot_read = std::string("cannot read ") + o0_sym;
+  Fd src;
+  src.fd = open(o0_sym, O_RDONLY);
   struct stat sb;
-  if (src.fd < 0 || fstat(src.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) throw RsError(RS_E_INVALID, std::string("cannot read ") + o0_sym);
+  if (src.fd < 0 || fstat(src.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) throw RsError(RS_E_INVALID, cannot_read);
   const uint64_t N = (uint64_t)sb.st_size;
   uint64_t chunk = env_u64("RS_SYM_CHUNK", kSymChunk, kSymChunkMin, kSymChunkMax);  // (read on every call)
   while (chunk & (chunk - 1)) chunk &= chunk - 1;  // a power of two (rounded down)
@@ -286,69 +283,31 @@ static void write_sym_device(rs_engine *E, const char *o0_sym, const char *path,
   uint64_t out_size = 0;
   uint8_t *out = nullptr;
   double t_in = t0, t_valid = t0;
-  struct Events {
-    hipEvent_t e[kRrBufs + 2] = {};  // the staging buffers' copies; [kRrBufs], [kRrBufs + 1] around k_sym_emit
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
+  Events<2> emit(hipEventDefault);  // around k_sym_emit
   if (N) {
     uint8_t *in = A.get<uint8_t>("sym.in", g.n_load);
     uint64_t *cdelta = A.get<uint64_t>("sym.cdelta", n_chunks), *coff = A.get<uint64_t>("sym.coff", n_chunks);
     unsigned long long *tot = A.get<unsigned long long>("sym.tot", 4);
-    const uint64_t stage = std::min<uint64_t>(kRrStage, N), nst = (N + stage - 1) / stage;
-    uint8_t *pool = (uint8_t *)pin_get(E, kPinStage, kRrBufs * stage);
     unsigned long long *h_tot = (unsigned long long *)pin_get(E, kPinRead, kPinRb);  // pinned read-back words [0..3]
-    for (int b = 0; b < kRrBufs; ++b) HC(hipEventCreateWithFlags(&evs.e[b], hipEventDisableTiming));
-    HC(hipEventCreate(&evs.e[kRrBufs]));
-    HC(hipEventCreate(&evs.e[kRrBufs + 1]));
-    HC(hipMemsetAsync(tot, 0, 32, stc));
-    int io_rc = 0;  // the thread's verdict (read after the join): 1 file, 2 HIP
-    uint8_t last = '\n';
-    const int fd = src.fd, device = E->device;
     const size_t lds_count = g.C + kSymHalo + 16, lds_emit = g.C + kSymHalo + 2 * 256 * sizeof(int);
-    struct Joined {
-      std::thread th;
-      ~Joined() {
-        if (th.joinable()) th.join();
-      }
-    } reader;
-    reader.th = std::thread([&, fd, device, stc]() {
-      if (hipSetDevice(device) != hipSuccess) { io_rc = 2; return; }
-      for (uint64_t i = 0; i < nst; ++i) {
-        const int b = (int)(i % kRrBufs);
-        if (i >= (uint64_t)kRrBufs && hipEventSynchronize(evs.e[b]) != hipSuccess) { io_rc = 2; break; }
-        const uint64_t off = i * stage, len = std::min(stage, N - off);
-        uint8_t *buf = pool + (uint64_t)b * stage;
-        for (uint64_t got = 0; got < len;) {
-          const ssize_t k = pread(fd, buf + got, len - got, (off_t)(off + got));
-          if (k <= 0) { io_rc = 1; break; }
-          got += (uint64_t)k;
-        }
-        if (io_rc) break;
-        if (i + 1 == nst) last = buf[len - 1];
-        if (hipMemcpyAsync(in + off, buf, len, hipMemcpyHostToDevice, stc) != hipSuccess ||
-            hipEventRecord(evs.e[b], stc) != hipSuccess) {
-          io_rc = 2;
-          break;
-        }
-        const uint64_t c0 = off / g.C, nc = (len + g.C - 1) / g.C;  // (stage: 32 MiB, or the one buffer of a smaller file)
-        hipLaunchKernelGGL(k_sym_count, dim3((unsigned)std::min<uint64_t>(nc, 65536)), dim3(256), lds_count, stc, (const uint8_t *)in, g, c0,
-                           nc, l2w, n_labels, cdelta, tot);
-        if (hipGetLastError() != hipSuccess) { io_rc = 2; break; }
-      }
-      if (hipStreamSynchronize(stc) != hipSuccess && !io_rc) io_rc = 2;  // the pool is free again; the file has landed and is counted
-    });
-    reader.th.join();
-    if (io_rc == 1) throw RsError(RS_E_INVALID, std::string("cannot read ") + o0_sym);
-    if (io_rc) throw RsError(RS_E_HIP, "rs_engine_write_sym: the upload of the .sym failed");
+    uint8_t last = '\n';
+    {
+      const int fd = src.fd;
+      StageIn up(E, N, g.C);
+      HC(hipMemsetAsync(tot, 0, 32, stc));
+      up.send(in, N, cannot_read, [fd](uint8_t *buf, uint64_t off, uint64_t len) { return pread_all(fd, buf, len, off); },
+              [&](const uint8_t *buf, uint64_t off, uint64_t len) {
+                if (off + len == N) last = buf[len - 1];
+                const uint64_t c0 = off / g.C, nc = (len + g.C - 1) / g.C;
+                hipLaunchKernelGGL(k_sym_count, dim3((unsigned)std::min<uint64_t>(nc, 65536)), dim3(256), lds_count, stc, (const uint8_t *)in, g,
+                                   c0, nc, l2w, n_labels, cdelta, tot);
+                HC(hipGetLastError());
+              });
+      HC(hipStreamSynchronize(stc));  // the file has landed and is counted
+    }
     t_in = now_ms();
     // ---- the chunks' offsets, the totals, the verdict
-    size_t tb = 0;
-    HC(rocprim::exclusive_scan(nullptr, tb, cdelta, coff, (uint64_t)0, (size_t)n_chunks, rocprim::plus<uint64_t>(), st));
-    void *tmp = A.get<uint8_t>("sym.scan", tb);
-    HC(rocprim::exclusive_scan(tmp, tb, cdelta, coff, (uint64_t)0, (size_t)n_chunks, rocprim::plus<uint64_t>(), st));
+    excl_scan(A, "sym.scan", st, (const uint64_t *)cdelta, coff, (uint64_t)0, n_chunks, rocprim::plus<uint64_t>());
     HC(hipMemcpyAsync(h_tot, tot, 32, hipMemcpyDeviceToHost, st));
     HC(hipStreamSynchronize(st));
     if (h_tot[3]) throw RsError(RS_E_INVALID, "bad sym file: a NUL byte");
@@ -360,30 +319,19 @@ static void write_sym_device(rs_engine *E, const char *o0_sym, const char *path,
     t_valid = now_ms();
     if (out_size) {
       out = A.get<uint8_t>("sym.out", out_size);
-      HC(hipEventRecord(evs.e[kRrBufs], st));
+      HC(hipEventRecord(emit.e[0], st));
       hipLaunchKernelGGL(k_sym_emit, dim3((unsigned)std::min<uint64_t>(n_chunks, 65536)), dim3(256), lds_emit, st, (const uint8_t *)in, g,
                          n_chunks, l2w, n_labels, (const uint64_t *)coff, out, out_size);
       HC(hipGetLastError());
-      HC(hipEventRecord(evs.e[kRrBufs + 1], st));
+      HC(hipEventRecord(emit.e[1], st));
     }
   }
-  // ---- the file (its blocks up front, while k_sym_emit runs), then the image through ImageOut
-  ImageOut io;
-  io.prepare(E, out_size);
-  dst.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (dst.fd < 0) throw RsError(RS_E_INVALID, std::string("cannot write ") + path);
-  std::atomic<bool> io_err{false};
-  if (out_size && posix_fallocate(dst.fd, 0, (off_t)out_size) != 0 && ftruncate(dst.fd, (off_t)out_size) != 0) io_err = true;
+  // ---- the file (its blocks up front, while k_sym_emit runs), then the image
   float emit_ms = 0;
-  if (out_size) {
-    HC(hipEventSynchronize(evs.e[kRrBufs + 1]));
-    HC(hipEventElapsedTime(&emit_ms, evs.e[kRrBufs], evs.e[kRrBufs + 1]));
-    io.run(st, dst.fd, out, out_size, 0, io_err);
-  }
-  const int fd = dst.fd;
-  dst.fd = -1;
-  if (close(fd) != 0) io_err = true;
-  if (io_err) throw RsError(RS_E_INVALID, "write error");
+  write_image_file(E, path, {}, {}, out, out_size, st, [&] {
+    HC(hipEventSynchronize(emit.e[1]));
+    HC(hipEventElapsedTime(&emit_ms, emit.e[0], emit.e[1]));
+  });
   const double t_end = now_ms();
   E->stats.sym_write_ms = t_end - t0;
   E->stats.sym_in_ms = t_in - t0;

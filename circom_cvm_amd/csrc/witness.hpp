@@ -29,7 +29,7 @@
 // A key >= n_labels sets an error bit instead of being gathered.  Positions are 64-bit.  Empty parts launch
 // nothing.  The result does not depend on the grid or on the chunk.
 #pragma once
-// (included by engine.hip inside namespace rs, after json_write.hpp: json_stage_up, ImageOut, pin_get)
+// (included by engine.hip inside namespace rs, after stage_io.hpp: StageIn, write_image_file)
 
 constexpr uint64_t kWitChunk = 1024, kWitChunkMin = 64, kWitChunkMax = 8192;  // a power of two (LDS: 8 B an entry)
 constexpr int kWitErrRange = 1, kWitErrOne = 2, kWitErrKey = 4, kWitErrWire = 8;
@@ -243,33 +243,14 @@ static void wit_upload(rs_engine *E, uint64_t n, uint32_t n8, uint32_t n8_file, 
   Fe *wm = A.get<Fe>("wit.w", n);
   uint8_t *raw = A.get<uint8_t>("wit.raw", n * n8);
   unsigned long long *res = A.get<unsigned long long>("wit.res", kWitRes);
-  const uint64_t per = std::min<uint64_t>(kRrStage / n8, n), stage = per * n8;  // values, bytes a buffer
-  uint8_t *pool = (uint8_t *)pin_get(E, kPinStage, kRrBufs * stage);
   unsigned long long *h = (unsigned long long *)pin_get(E, kPinRead, kPinRb);
-  struct Events {
-    hipEvent_t e[kRrBufs] = {};
-    ~Events() {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  for (hipEvent_t &x : evs.e) HC(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-  struct Drain {  // the pool is free again on every way out
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-  } drain{stc};
+  StageIn up(E, n * n8, n8);  // (a buffer: whole values)
   HC(hipMemsetAsync(res, 0, 8 * kWitRes, stc));
-  uint64_t seq = 0;
-  for (uint64_t i0 = 0; i0 < n; i0 += per, ++seq) {
-    const int b = (int)(seq % kRrBufs);
-    if (seq >= (uint64_t)kRrBufs) HC(hipEventSynchronize(evs.e[b]));
-    const uint64_t cnt = std::min(per, n - i0);
-    uint8_t *buf = pool + (uint64_t)b * stage;
-    if (!fill(buf, i0, cnt)) throw RsError(RS_E_INVALID, "cannot read the witness's values");
-    HC(hipMemcpyAsync(raw + i0 * n8, buf, cnt * n8, hipMemcpyHostToDevice, stc));
-    HC(hipEventRecord(evs.e[b], stc));
-    launch(stc, k_wit_prepare, cnt, (const uint8_t *)raw, n8, i0, cnt, F, wm, res);
-  }
+  up.send(raw, n * n8, "cannot read the witness's values",
+          [&](uint8_t *buf, uint64_t off, uint64_t len) { return fill(buf, off / n8, len / n8); },
+          [&](const uint8_t *, uint64_t off, uint64_t len) {
+            launch(stc, k_wit_prepare, len / n8, (const uint8_t *)raw, n8, off / n8, len / n8, F, wm, res);
+          });
   HC(hipMemcpyAsync(h, res + 12, 8, hipMemcpyDeviceToHost, stc));
   HC(hipStreamSynchronize(stc));
   if (h[0] & kWitErrRange) throw RsError(RS_E_INVALID, "witness: a value is not below the prime");
@@ -296,16 +277,15 @@ struct WitSrc {
 };
 
 // One rs_lc of the caller (host arrays) into the writers' arena under `nm`, through the staging pool
-static void wit_stage_block(rs_engine *E, const rs_lc &L, const char *what, const std::string &nm, uint8_t *pool, uint64_t stage,
-                            hipEvent_t *ev, uint64_t &seq, WitSrc &s, int q) {
+static void wit_stage_block(rs_engine *E, const rs_lc &L, const char *what, const std::string &nm, StageIn &up, WitSrc &s, int q) {
   const uint64_t n = L.n_rows, nnz = L.nnz;
   if (!L.ptr || (nnz && (!L.col || !L.val))) throw RsError(RS_E_INVALID, std::string(what) + " block: rows without ptr / col / val");
   uint64_t *ptr = E->SA.get<uint64_t>(nm + ".ptr", n + 1);
   uint32_t *col = E->SA.get<uint32_t>(nm + ".col", nnz);
   uint64_t *val = E->SA.get<uint64_t>(nm + ".val", 4 * nnz);
-  json_stage_up(E, pool, stage, ev, seq, ptr, L.ptr, 8 * (n + 1));
-  json_stage_up(E, pool, stage, ev, seq, col, L.col, 4 * nnz);
-  json_stage_up(E, pool, stage, ev, seq, val, L.val, 32 * nnz);
+  up.send(ptr, L.ptr, 8 * (n + 1));
+  up.send(col, L.col, 4 * nnz);
+  up.send(val, L.val, 32 * nnz);
   s.ptr[q] = ptr;
   s.col[q] = col;
   s.val[q] = val;
@@ -410,21 +390,7 @@ static void check_witness_device(rs_engine *E, const rs_input *in, uint32_t what
       all += 4 * n_log + 8 * (n_log + 1) + 36 * log_nnz;
     }
     if (all) {
-      const uint64_t stage = std::min<uint64_t>(kRrStage, (all + 4095) & ~4095ull);
-      uint8_t *pool = (uint8_t *)pin_get(E, kPinStage, kRrBufs * stage);
-      struct Events {
-        hipEvent_t e[kRrBufs] = {};
-        ~Events() {
-          for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-        }
-      } evs;
-      for (hipEvent_t &x : evs.e) HC(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-      struct Drain {  // the pool is free again on every way out
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-      } drain{E->stc};
-      uint64_t seq = 0;
+      StageIn up(E, (all + 4095) & ~4095ull);
       if (what & RS_WIT_INPUT) {
         const char *nm[3] = {"cons_eq", "eq", "linear"};
         for (int q = 0; q < 3; ++q) {
@@ -433,16 +399,16 @@ static void check_witness_device(rs_engine *E, const rs_input *in, uint32_t what
           s.n = lin[q]->n_rows;
           s.nparts = 1;
           s.cls = q;
-          wit_stage_block(E, *lin[q], nm[q], std::string("wit.in.") + nm[q], pool, stage, evs.e, seq, s, 0);
+          wit_stage_block(E, *lin[q], nm[q], std::string("wit.in.") + nm[q], up, s, 0);
         }
         if (in->nl_a.n_rows) {
           WitSrc &s = src[n_src++];
           s.n = in->nl_a.n_rows;
           s.nparts = 3;
           s.cls = RS_WITC_NONLINEAR;
-          wit_stage_block(E, in->nl_a, "nl_a", "wit.in.nl_a", pool, stage, evs.e, seq, s, 0);
-          wit_stage_block(E, in->nl_b, "nl_b", "wit.in.nl_b", pool, stage, evs.e, seq, s, 1);
-          wit_stage_block(E, in->nl_c, "nl_c", "wit.in.nl_c", pool, stage, evs.e, seq, s, 2);
+          wit_stage_block(E, in->nl_a, "nl_a", "wit.in.nl_a", up, s, 0);
+          wit_stage_block(E, in->nl_b, "nl_b", "wit.in.nl_b", up, s, 1);
+          wit_stage_block(E, in->nl_c, "nl_c", "wit.in.nl_c", up, s, 2);
         }
         rep->checked[RS_WITC_CONS_EQ] = in->cons_eq.n_rows;
         rep->checked[RS_WITC_EQ] = in->eq.n_rows;
@@ -452,10 +418,10 @@ static void check_witness_device(rs_engine *E, const rs_input *in, uint32_t what
       if (n_log) {
         uint32_t *from = A.get<uint32_t>("wit.log.from", n_log), *key = A.get<uint32_t>("wit.log.key", log_nnz);
         uint64_t *ptr = A.get<uint64_t>("wit.log.ptr", n_log + 1), *val = A.get<uint64_t>("wit.log.val", 4 * log_nnz);
-        json_stage_up(E, pool, stage, evs.e, seq, from, E->log_from.data(), 4 * n_log);
-        json_stage_up(E, pool, stage, evs.e, seq, ptr, E->log_ptr.data(), 8 * (n_log + 1));
-        json_stage_up(E, pool, stage, evs.e, seq, key, E->log_key.data(), 4 * log_nnz);
-        json_stage_up(E, pool, stage, evs.e, seq, val, E->log_val.data(), 32 * log_nnz);
+        up.send(from, E->log_from.data(), 4 * n_log);
+        up.send(ptr, E->log_ptr.data(), 8 * (n_log + 1));
+        up.send(key, E->log_key.data(), 4 * log_nnz);
+        up.send(val, E->log_val.data(), 32 * log_nnz);
         WitSrc &s = src[5];  // (evaluated last, after the output)
         s.n = n_log;
         s.nparts = 1;
@@ -536,23 +502,6 @@ static void write_wtns_device(rs_engine *E, const char *path) {
   HC(hipStreamSynchronize(st));
   if (h[0] & kWitErrWire) throw RsError(RS_E_INTERNAL, "rs_engine_write_wtns: a wire is not below n_wires");
   const std::vector<uint8_t> head = wtns::head_bytes(n8, E->wit_prime, nw);
-  ImageOut io;
-  io.prepare(E, total);
-  struct Fd {
-    int fd;
-    ~Fd() {
-      if (fd >= 0) close(fd);
-    }
-  } dst{open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644)};
-  if (dst.fd < 0) throw RsError(RS_E_INVALID, std::string("cannot write ") + path);
-  std::atomic<bool> io_err{false};
-  const uint64_t fsize = head.size() + total;
-  if (posix_fallocate(dst.fd, 0, (off_t)fsize) != 0 && ftruncate(dst.fd, (off_t)fsize) != 0) io_err = true;
-  if (!pwrite_all(dst.fd, head.data(), head.size(), 0)) io_err = true;
-  if (total) io.run(st, dst.fd, img, total, head.size(), io_err);
-  const int fd = dst.fd;
-  dst.fd = -1;
-  if (close(fd) != 0) io_err = true;
-  if (io_err) throw RsError(RS_E_INVALID, "write error");
+  write_image_file(E, path, {head.data(), head.size()}, {}, img, total, st);
 }
 #endif  // __HIPCC__

@@ -118,17 +118,6 @@ struct Head {
   uint64_t off2 = 0;  // where section 2's body starts in the file (n8 * n bytes)
 };
 
-inline bool pread_all(int fd, void *dst, uint64_t n, uint64_t off) {
-  uint8_t *d = (uint8_t *)dst;
-  while (n) {
-    const ssize_t g = pread(fd, d, n, (off_t)off);
-    if (g <= 0) return false;
-    d += g;
-    n -= (uint64_t)g;
-    off += (uint64_t)g;
-  }
-  return true;
-}
 inline uint32_t prime_id_of(const uint64_t p[4]) {
   for (uint32_t i = 0; i < 8; ++i)
     if (eq4(p, kPrimes[i])) return i;
@@ -187,13 +176,7 @@ inline bool read_head(int fd, uint64_t size, Head &H) {
   return true;
 }
 
-struct Fd {
-  int fd;
-  ~Fd() {
-    if (fd >= 0) close(fd);
-  }
-};
-// Opens `path` and parses its header; the caller owns f.fd.
+// Opens `path` and parses its header; the caller owns f.fd (Fd, pread_all: host_common.hpp).
 inline bool open_head(const char *path, Fd &f, Head &H) {
   f.fd = open(path, O_RDONLY);
   struct stat sb;
@@ -213,7 +196,7 @@ inline void witness_free(rs_witness *w) {
 inline int read_wtns(const char *path, rs_witness **out) {
   if (!path || !out) { set_error("rs_read_wtns: null argument"); return RS_E_INVALID; }
   *out = nullptr;
-  Fd f{-1};
+  Fd f;
   Head H;
   if (!open_head(path, f, H)) return RS_E_INVALID;
   // (section 2 lies inside the file, so 32 n <= 4 * the file's size: checked before this allocation)

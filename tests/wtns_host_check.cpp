@@ -2,7 +2,9 @@
 // evaluation of a witness), driven by tests/test_wtns_abi.py under the address and undefined-behaviour
 // sanitizers (built together with csrc/host_common.cpp: the error text and the prime table).
 //   wtns_host_check <scratch file> <good.wtns> [<malformed.wtns> ...]
-// The good file is read, written back (the same bytes) and then cut at every byte length: each cut must
+// First the file helpers it reads through (Fd, pread_all, pwrite_all of csrc/host_common.hpp) on the scratch
+// file, a short read and a short write among them.  Then
+// the good file is read, written back (the same bytes) and then cut at every byte length: each cut must
 // be refused with RS_E_INVALID, and so must every malformed file.  Last, a three-row system over F_257 is
 // evaluated on a witness that satisfies it and on one that does not.  Prints `ok` and exits 0, or says
 // what went wrong and exits 1.
@@ -10,6 +12,9 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include <csignal>
+#include <sys/resource.h>
 
 #include "wtns_io.hpp"
 
@@ -79,9 +84,45 @@ static int small_evaluation() {
   return 0;
 }
 
+// Fd, pread_all and pwrite_all (host_common.hpp; the device path's staging code uses them too): a read that
+// the file ends before is refused whole, and a write that the file-size limit cuts short -- pwrite returns
+// fewer bytes than asked, then fails -- is reported, with the bytes that fit on disk.
+static int short_read_and_write(const char *scratch) {
+  const uint8_t src[16] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
+  uint8_t buf[16] = {};
+  {
+    Fd f;
+    f.fd = open(scratch, O_RDWR | O_CREAT | O_TRUNC, 0644);
+    if (f.fd < 0) return fail("cannot open the scratch file");
+    if (!pwrite_all(f.fd, src, 10, 0) || !pwrite_all(f.fd, src, 0, 99)) return fail("pwrite_all: a plain write failed");
+    if (!pread_all(f.fd, buf, 10, 0) || memcmp(buf, src, 10) != 0) return fail("pread_all: the bytes written do not come back");
+    if (!pread_all(f.fd, buf, 4, 6) || memcmp(buf, src + 6, 4) != 0) return fail("pread_all: wrong bytes at an offset");
+    if (pread_all(f.fd, buf, 11, 0) || pread_all(f.fd, buf, 1, 10)) return fail("pread_all: a read past the end of the file succeeded");
+    if (!pread_all(f.fd, buf, 0, 10)) return fail("pread_all: an empty read failed");
+    struct rlimit old, cut;
+    if (getrlimit(RLIMIT_FSIZE, &old) != 0) return fail("getrlimit");
+    cut = old;
+    cut.rlim_cur = 12;
+    signal(SIGXFSZ, SIG_IGN);
+    if (setrlimit(RLIMIT_FSIZE, &cut) != 0) return fail("setrlimit");
+    const bool wrote = pwrite_all(f.fd, src, 16, 4);  // 8 bytes fit below the limit
+    setrlimit(RLIMIT_FSIZE, &old);
+    signal(SIGXFSZ, SIG_DFL);
+    if (wrote) return fail("pwrite_all: a write cut short by the file-size limit was reported whole");
+    if (!pread_all(f.fd, buf, 12, 0) || memcmp(buf, src, 4) != 0 || memcmp(buf + 4, src, 8) != 0 || pread_all(f.fd, buf, 1, 12))
+      return fail("pwrite_all: the short write did not leave the bytes that fit");
+    const int fd = f.release();
+    if (f.fd != -1 || close(fd) != 0) return fail("Fd::release");
+  }
+  Fd none;  // (closes nothing)
+  if (pread_all(none.fd, buf, 1, 0) || pwrite_all(none.fd, src, 1, 0)) return fail("a closed descriptor was read or written");
+  return 0;
+}
+
 int main(int argc, char **argv) {
   if (argc < 3) return fail("usage: wtns_host_check scratch good.wtns [malformed.wtns ...]");
   const char *scratch = argv[1];
+  if (short_read_and_write(scratch)) return 1;
   std::vector<uint8_t> good;
   if (!slurp(argv[2], good)) return fail("cannot read the good file");
   rs_witness *w = nullptr;
