@@ -171,6 +171,20 @@ class RsWitnessReport(C.Structure):
         return d
 
 
+class RsLiftReport(C.Structure):
+    """rs_lift_report: what a lift found (lifted / free labels, shadowed entries, levels, pairs evaluated)."""
+    _fields_ = [("n_labels", C.c_uint64), ("n_wires", C.c_uint64), ("lifted", C.c_uint64), ("free_labels", C.c_uint64),
+                ("shadowed", C.c_uint64), ("levels", C.c_uint64), ("entries", C.c_uint64),
+                ("in_ms", C.c_double), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+    def counts(self):
+        """The report apart from the times."""
+        return tuple(int(getattr(self, k)) for k, t in self._fields_ if t is C.c_uint64)
+
+
 class RsDag(C.Structure):
     """rs_dag: the component DAG rs_flatten_dag expands."""
     _fields_ = [("prime_id", C.c_uint32), ("prime", C.c_uint64 * 4),
@@ -238,6 +252,13 @@ SYMBOLS = [
     ("rs_engine_load_wtns", C.c_int, [C.c_void_p, C.c_char_p]),
     ("rs_engine_check_witness", C.c_int, [C.c_void_p, C.POINTER(RsInput), C.c_uint32, C.POINTER(RsWitnessReport)]),
     ("rs_engine_write_wtns", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rs_lift_witness", C.c_int, [C.POINTER(RsOutput), C.POINTER(RsWitness), C.POINTER(C.POINTER(RsWitness)),
+                                  C.POINTER(RsLiftReport)]),
+    ("rs_lift_witness_device", C.c_int, [C.c_int, C.POINTER(RsOutput), C.POINTER(RsWitness),
+                                         C.POINTER(C.POINTER(RsWitness)), C.POINTER(RsLiftReport)]),
+    ("rs_engine_lift_witness", C.c_int, [C.c_void_p, C.POINTER(RsLiftReport)]),
+    ("rs_engine_fetch_witness", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(RsWitness))]),
+    ("rs_engine_write_wtns_resident", C.c_int, [C.c_void_p, C.c_char_p]),
 ]
 
 _LIB = None
@@ -424,6 +445,23 @@ class Engine:
         """rs_engine_write_wtns: the resident witness projected onto the last result's wires."""
         check(lib().rs_engine_write_wtns(self._h, path.encode()))
 
+    def lift_witness(self) -> RsLiftReport:
+        """rs_engine_lift_witness: the resident wire witness (one value per wire of the last result) replaced
+        by the lifted one (one value per --O0 label), through the last run's substitution log."""
+        rep = RsLiftReport()
+        check(lib().rs_engine_lift_witness(self._h, C.byref(rep)))
+        return rep
+
+    def fetch_witness(self) -> "Witness":
+        """rs_engine_fetch_witness: the resident witness, canonical (library-owned)."""
+        p = C.POINTER(RsWitness)()
+        check(lib().rs_engine_fetch_witness(self._h, C.byref(p)))
+        return Witness(ptr=p)
+
+    def write_wtns_resident(self, path: str):
+        """rs_engine_write_wtns_resident: the resident witness as it is, as a .wtns."""
+        check(lib().rs_engine_write_wtns_resident(self._h, path.encode()))
+
     def json_stats(self) -> RsJsonStats:
         s = RsJsonStats()
         check(lib().rs_engine_json_stats(self._h, C.byref(s)))
@@ -488,6 +526,22 @@ def check_witness(w, what: int, inp: RsInput | None = None, out: RsOutput | None
     check(lib().rs_check_witness(C.byref(inp) if inp is not None else None, C.byref(out) if out is not None else None,
                                  C.byref(w.c if isinstance(w, Witness) else w), what, C.byref(rep)))
     return rep
+
+
+def lift_witness(v, out: RsOutput):
+    """rs_lift_witness: the host lift of the wire witness `v` (a Witness or an RsWitness) through `out`'s
+    log -> (Witness, RsLiftReport)."""
+    p, rep = C.POINTER(RsWitness)(), RsLiftReport()
+    check(lib().rs_lift_witness(C.byref(out), C.byref(v.c if isinstance(v, Witness) else v), C.byref(p), C.byref(rep)))
+    return Witness(ptr=p), rep
+
+
+def lift_witness_device(v, out: RsOutput, device: int = 0):
+    """rs_lift_witness_device: the same on the GPU, as a one-shot -> (Witness, RsLiftReport)."""
+    p, rep = C.POINTER(RsWitness)(), RsLiftReport()
+    check(lib().rs_lift_witness_device(device, C.byref(out), C.byref(v.c if isinstance(v, Witness) else v), C.byref(p),
+                                       C.byref(rep)))
+    return Witness(ptr=p), rep
 
 
 def field_size_bytes(p: int) -> int:

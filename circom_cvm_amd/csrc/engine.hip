@@ -734,6 +734,7 @@ static U3 excl_scan_u3(rs_engine *E, const U3 *in, U3 *out, uint64_t n, const ch
 #include "sym_write.hpp"
 #include "json_write.hpp"
 #include "witness.hpp"
+#include "lift.hpp"
 #include "output.hpp"
 __global__ void k_pack3(const uint64_t *a, const uint64_t *b, const uint64_t *c, uint64_t n, U3 *out) {
   for (uint64_t i = gtid(); i < n; i += gstride()) out[i] = U3{a[i], b[i], c[i]};
@@ -3545,18 +3546,22 @@ int rs_write_substitution_json_device(int device, const char *path, const rs_out
 }
 
 // ---- the witness on the device (witness.hpp)
+namespace rs {
+// rs_engine_load_witness's body: `w` resident on E
+static void load_witness_values(rs_engine *E, const rs_witness *w, const char *who) {
+  uint64_t p[4];
+  if (!wtns::witness_prime(w, p)) throw RsError(RS_E_INVALID, std::string(who) + ": bad prime or field size");
+  if (w->n == 0 || w->n > 0x7fffffffull) throw RsError(RS_E_INVALID, std::string(who) + ": the witness needs 1 .. 2^31 - 1 values");
+  const uint64_t *val = w->val;
+  wit_upload(E, w->n, 32, w->n8, p, wtns::prime_id_of(p), [val](uint8_t *dst, uint64_t i0, uint64_t cnt) {
+    memcpy(dst, val + 4 * i0, 32 * cnt);
+    return true;
+  });
+}
+}  // namespace rs
 int rs_engine_load_witness(rs_engine *E, const rs_witness *w) {
   if (!E || !w || (w->n && !w->val)) { set_error("rs_engine_load_witness: null argument"); return RS_E_INVALID; }
-  return engine_call(E, true, [&] {
-    uint64_t p[4];
-    if (!wtns::witness_prime(w, p)) throw RsError(RS_E_INVALID, "rs_engine_load_witness: bad prime or field size");
-    if (w->n == 0 || w->n > 0x7fffffffull) throw RsError(RS_E_INVALID, "rs_engine_load_witness: the witness needs 1 .. 2^31 - 1 values");
-    const uint64_t *val = w->val;
-    wit_upload(E, w->n, 32, w->n8, p, wtns::prime_id_of(p), [val](uint8_t *dst, uint64_t i0, uint64_t cnt) {
-      memcpy(dst, val + 4 * i0, 32 * cnt);
-      return true;
-    });
-  });
+  return engine_call(E, true, [&] { load_witness_values(E, w, "rs_engine_load_witness"); });
 }
 
 int rs_engine_load_wtns(rs_engine *E, const char *path) {
@@ -3581,6 +3586,57 @@ int rs_engine_check_witness(rs_engine *E, const rs_input *in, uint32_t what, rs_
 int rs_engine_write_wtns(rs_engine *E, const char *path) {
   if (!E || !path) { set_error("rs_engine_write_wtns: null argument"); return RS_E_INVALID; }
   return engine_call(E, true, [&] { write_wtns_device(E, path); });
+}
+
+// ---- the lift (lift.hpp)
+int rs_engine_lift_witness(rs_engine *E, rs_lift_report *rep) {
+  if (!E || !rep) { set_error("rs_engine_lift_witness: null argument"); return RS_E_INVALID; }
+  return engine_call(E, true, [&] { lift_engine(E, rep); });
+}
+
+int rs_engine_fetch_witness(rs_engine *E, rs_witness **w) {
+  if (w) *w = nullptr;
+  if (!E || !w) { set_error("rs_engine_fetch_witness: null argument"); return RS_E_INVALID; }
+  return engine_call(E, true, [&] { fetch_witness_device(E, w); });
+}
+
+int rs_engine_write_wtns_resident(rs_engine *E, const char *path) {
+  if (!E || !path) { set_error("rs_engine_write_wtns_resident: null argument"); return RS_E_INVALID; }
+  return engine_call(E, true, [&] { write_wtns_resident_device(E, path); });
+}
+
+// The one-shot: v, label_to_wire and the log of `out` go to the device; nothing else of `out` is read.
+int rs_lift_witness_device(int device, const rs_output *out, const rs_witness *v, rs_witness **w, rs_lift_report *rep) {
+  if (w) *w = nullptr;
+  if (!out || !v || !w || !rep || (v->n && !v->val) || (out->n_labels && !out->label_to_wire) ||
+      (out->n_log && (!out->log_from || !out->log_to.ptr)) || (out->n_log && out->log_to.nnz && (!out->log_to.col || !out->log_to.val))) {
+    set_error("rs_lift_witness_device: null argument");
+    return RS_E_INVALID;
+  }
+  return one_shot(device, [&](rs_engine *E) {
+    if (v->n != out->n_wires)
+      throw RsError(RS_E_INVALID, "rs_lift_witness_device: the witness has " + std::to_string(v->n) + " values, the result " +
+                                      std::to_string(out->n_wires) + " wires");
+    if (out->n_labels == 0 || out->n_labels > 0x7fffffffull) throw RsError(RS_E_INVALID, "rs_lift_witness_device: the result needs 1 .. 2^31 - 1 labels");
+    if (v->n == 0) throw RsError(RS_E_INVALID, "rs_lift_witness_device: w[0] is not 1 (key 0 is the constant)");
+    load_witness_values(E, v, "rs_lift_witness_device");
+    int32_t *l2w = E->SA.get<int32_t>("lift.l2w", out->n_labels);
+    h2d(E, l2w, out->label_to_wire, 4 * out->n_labels);
+    LiftIn in;
+    in.n_labels = out->n_labels;
+    in.n_wires = out->n_wires;
+    in.l2w = l2w;
+    in.n = out->n_log;
+    if (in.n) {
+      in.nnz = out->log_to.nnz;
+      in.from = out->log_from;
+      in.ptr = out->log_to.ptr;
+      in.key = out->log_to.col;
+      in.val = out->log_to.val;
+    }
+    lift_device(E, in, rep, "rs_lift_witness_device");
+    fetch_witness_device(E, w);
+  });
 }
 
 void *rs_host_alloc(uint64_t bytes) {

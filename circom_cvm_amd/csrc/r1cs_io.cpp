@@ -638,3 +638,6 @@ int rs_write_wtns(const char *path, const rs_witness *w, const rs_output *out) {
 int rs_check_witness(const rs_input *in, const rs_output *out, const rs_witness *w, uint32_t what, rs_witness_report *rep) {
   return rs::wtns::check_witness(in, out, w, what, rep);
 }
+int rs_lift_witness(const rs_output *out, const rs_witness *v, rs_witness **w, rs_lift_report *rep) {
+  return rs::wtns::lift_witness(out, v, w, rep);
+}

@@ -26,6 +26,8 @@
 //                fmul(a, b) against c, c against 0, or w[from] against the dot.  Failures are counted and
 //                the smallest failing row found per lane, reduced over the wave, one atomicAdd and one
 //                atomicMin per wave that saw a failure.
+// k_wit_dot's body is the template wit_dot_chunks: the lift (lift.hpp, k_lift_dot) runs it over a level's
+// virtual rows, whose entries lie elsewhere in the log (WitVirt); the check's instance reads entry e at e.
 // A key >= n_labels sets an error bit instead of being gathered.  Positions are 64-bit.  Empty parts launch
 // nothing.  The result does not depend on the grid or on the chunk.
 #pragma once
@@ -67,18 +69,31 @@ struct WitPart {
 // LDS (dynamic, 16 B aligned): 2 x 256 Fe (the scan's two rows), 256 u64 (the lanes' rows), the carry
 // (Fe + its row), then C + 2 row pointers
 constexpr size_t kWitLdsFixed = 2 * 256 * sizeof(Fe) + 256 * 8 + sizeof(Fe) + 16;
-__global__ void __launch_bounds__(256) k_wit_dot(FieldP F, WitPart P, uint64_t n_rows, const Fe *wm, uint64_t n_labels, uint32_t C,
-                                                 uint64_t n_chunks, unsigned long long *res) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t wit_lds[];
+// The rows the lift evaluates (lift.hpp) are a virtual CSR: P.ptr holds the virtual pointers of a level's
+// rows, the entries [e0, e1) are theirs, and row r's entries lie at sptr[idx[r]] + (e - P.ptr[r]) of
+// col / val.  The check's rows are their own source: entry e of [0, nnz) is entry e.
+struct WitVirt {
+  const uint32_t *idx;   // virtual row -> source row
+  const uint64_t *sptr;  // the source's row pointers
+  uint64_t e0, e1;
+  int src_lds;           // the rows' source positions fit in LDS beside the pointer slice
+};
+// The body of k_wit_dot and k_lift_dot (kVirt).  lds: kWitLdsFixed + 8 (C + 2) bytes, with kVirt 8 (C + 2)
+// more (the rows' source positions beside their virtual pointers).
+template <bool kVirt>
+__device__ __forceinline__ void wit_dot_chunks(uint8_t *wit_lds, const FieldP &F, const WitPart &P, const WitVirt &V, uint64_t n_rows,
+                                               const Fe *wm, uint64_t n_labels, uint32_t C, uint64_t n_chunks, unsigned long long *res) {
   Fe *s_v = reinterpret_cast<Fe *>(wit_lds);
   uint64_t *s_row = reinterpret_cast<uint64_t *>(s_v + 512);
   Fe *s_carry = reinterpret_cast<Fe *>(s_row + 256);
   uint64_t *s_carry_row = reinterpret_cast<uint64_t *>(s_carry + 1);
   uint64_t *s_ptr = s_carry_row + 2;
+  uint64_t *s_src = s_ptr + C + 2;  // (kVirt)
   const uint32_t t = threadIdx.x;
+  const uint64_t e0 = kVirt ? V.e0 : 0, e1 = kVirt ? V.e1 : P.nnz;
   int bad = 0;
   for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-    const uint64_t lo = c * C, hi = lo + C < P.nnz ? lo + C : P.nnz;
+    const uint64_t lo = e0 + c * C, hi = lo + C < e1 ? lo + C : e1;
     // r0 / r1: the rows that hold entries lo / hi - 1 (the last row whose pointer is not above the entry)
     uint64_t a = 0, b = n_rows - 1;
     while (a < b) {
@@ -95,8 +110,11 @@ __global__ void __launch_bounds__(256) k_wit_dot(FieldP F, WitPart P, uint64_t n
     }
     const uint64_t nr = a - r0 + 1;  // rows of the slice; S[0 .. nr] their pointers
     const uint64_t *S = P.ptr + r0;
-    if (nr + 1 <= (uint64_t)C + 2) {
+    const bool in_lds = nr + 1 <= (uint64_t)C + 2;
+    if (in_lds) {
       for (uint64_t i = t; i <= nr; i += 256) s_ptr[i] = P.ptr[r0 + i];
+      if (kVirt && V.src_lds)
+        for (uint64_t i = t; i < nr; i += 256) s_src[i] = V.sptr[V.idx[r0 + i]];
       S = s_ptr;
     }
     if (t == 0) *s_carry_row = UINT64_MAX;
@@ -115,8 +133,10 @@ __global__ void __launch_bounds__(256) k_wit_dot(FieldP F, WitPart P, uint64_t n
         }
         i = u;
         row = r0 + i;
-        const uint32_t k = P.col[e];
-        if (k < n_labels) x = fmul(F, P.val[e], wm[k]);
+        // (kVirt: lanes on one row still read consecutive col / val)
+        const uint64_t se = kVirt ? (in_lds && V.src_lds ? s_src[i] : V.sptr[V.idx[row]]) + (e - S[i]) : e;
+        const uint32_t k = P.col[se];
+        if (k < n_labels) x = fmul(F, P.val[se], wm[k]);
         else bad |= kWitErrKey;
       }
       s_row[t] = row;
@@ -152,6 +172,12 @@ __global__ void __launch_bounds__(256) k_wit_dot(FieldP F, WitPart P, uint64_t n
   if (bad) atomicOr(res + 12, (unsigned long long)bad);
 }
 
+__global__ void __launch_bounds__(256) k_wit_dot(FieldP F, WitPart P, uint64_t n_rows, const Fe *wm, uint64_t n_labels, uint32_t C,
+                                                 uint64_t n_chunks, unsigned long long *res) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t wit_lds[];
+  wit_dot_chunks<false>(wit_lds, F, P, WitVirt{}, n_rows, wm, n_labels, C, n_chunks, res);
+}
+
 struct WitRows {
   uint64_t n;
   int nparts;            // 3: (A.w)(B.w) = C.w; 1: C.w = 0, or with `from`: w[from] = C.w
@@ -161,10 +187,11 @@ struct WitRows {
   uint32_t shift;        // log2 of the chunk
 };
 
-__device__ __forceinline__ Fe wit_row_dot(const FieldP &F, const WitPart &P, uint64_t r, uint32_t shift) {
+// (e0: where the part's chunks begin: 0 for the check, the level's first virtual entry for the lift)
+__device__ __forceinline__ Fe wit_row_dot(const FieldP &F, const WitPart &P, uint64_t r, uint32_t shift, uint64_t e0 = 0) {
   const uint64_t b = P.ptr[r], e = P.ptr[r + 1];
   if (b == e) return fe_zero();
-  const uint64_t c0 = b >> shift, c1 = (e - 1) >> shift;
+  const uint64_t c0 = (b - e0) >> shift, c1 = (e - 1 - e0) >> shift;
   if (c0 == c1) return P.dot[r];
   Fe s = P.tail[c0];
   for (uint64_t c = c0 + 1; c < c1; ++c) s = fadd(F, s, P.head[c]);
@@ -211,12 +238,13 @@ __global__ void k_wit_rows(FieldP F, WitRows R, const Fe *wm, uint64_t n_labels,
 }
 
 // A lane per label with a wire: its value, canonical and narrowed to n8 bytes, at image byte n8 * l2w[s].
-// l2w is the order-preserving rank of the kept labels: every byte has one writer.
+// l2w is the order-preserving rank of the kept labels: every byte has one writer.  l2w == nullptr: the
+// witness as it is (value s at n8 * s).
 __global__ void k_wit_project(FieldP F, const Fe *wm, const int32_t *l2w, uint64_t n_labels, uint64_t n_wires, uint32_t n8, uint8_t *img,
                               unsigned long long *res) {
   int bad = 0;
   for (uint64_t s = gtid(); s < n_labels; s += gstride()) {
-    const int32_t wire = l2w[s];
+    const int64_t wire = l2w ? (int64_t)l2w[s] : (int64_t)s;
     if (wire < 0) continue;
     if ((uint64_t)wire >= n_wires) {
       bad |= kWitErrWire;
@@ -290,6 +318,34 @@ static void wit_stage_block(rs_engine *E, const rs_lc &L, const char *what, cons
   s.col[q] = col;
   s.val[q] = val;
   s.nnz[q] = nnz;
+}
+
+// The substitution log (host arrays) into the writers' arena, through the staging pool: the check's and
+// the lift's source.  log_stage_bytes: what it sends, for the pool's size.
+static uint64_t log_stage_bytes(uint64_t n_log, uint64_t log_nnz) { return n_log ? 4 * n_log + 8 * (n_log + 1) + 36 * log_nnz : 0; }
+static void wit_stage_log(rs_engine *E, StageIn &up, const uint32_t *h_from, const uint64_t *h_ptr, const uint32_t *h_key,
+                          const uint64_t *h_val, uint64_t n_log, uint64_t log_nnz, WitSrc &s) {
+  Arena &A = E->SA;
+  uint32_t *from = A.get<uint32_t>("wit.log.from", n_log), *key = A.get<uint32_t>("wit.log.key", log_nnz);
+  uint64_t *ptr = A.get<uint64_t>("wit.log.ptr", n_log + 1), *val = A.get<uint64_t>("wit.log.val", 4 * log_nnz);
+  up.send(from, h_from, 4 * n_log);
+  up.send(ptr, h_ptr, 8 * (n_log + 1));
+  up.send(key, h_key, 4 * log_nnz);
+  up.send(val, h_val, 32 * log_nnz);
+  s.n = n_log;
+  s.nparts = 1;
+  s.cls = RS_WITC_LOG;
+  s.from = from;
+  s.ptr[0] = ptr;
+  s.col[0] = key;
+  s.val[0] = val;
+  s.nnz[0] = log_nnz;
+}
+// The engine's own log: its vectors agree
+static void log_arrays_agree(rs_engine *E) {
+  const uint64_t n_log = E->log_from.size(), log_nnz = E->log_key.size();
+  if (E->log_ptr.size() != n_log + 1 || E->log_ptr[n_log] != log_nnz || E->log_val.size() != 4 * log_nnz)
+    throw RsError(RS_E_INTERNAL, "the substitution log's arrays disagree");
 }
 
 // The rows of `s` against the resident witness: their failures into res[2 cls], res[2 cls + 1]
@@ -385,9 +441,8 @@ static void check_witness_device(rs_engine *E, const rs_input *in, uint32_t what
     }
     const uint64_t n_log = (what & RS_WIT_LOG) ? E->log_from.size() : 0, log_nnz = n_log ? E->log_key.size() : 0;
     if (n_log) {
-      if (E->log_ptr.size() != n_log + 1 || E->log_ptr[n_log] != log_nnz || E->log_val.size() != 4 * log_nnz)
-        throw RsError(RS_E_INTERNAL, "the substitution log's arrays disagree");
-      all += 4 * n_log + 8 * (n_log + 1) + 36 * log_nnz;
+      log_arrays_agree(E);
+      all += log_stage_bytes(n_log, log_nnz);
     }
     if (all) {
       StageIn up(E, (all + 4095) & ~4095ull);
@@ -415,23 +470,8 @@ static void check_witness_device(rs_engine *E, const rs_input *in, uint32_t what
         rep->checked[RS_WITC_LINEAR] = in->linear.n_rows;
         rep->checked[RS_WITC_NONLINEAR] = in->nl_a.n_rows;
       }
-      if (n_log) {
-        uint32_t *from = A.get<uint32_t>("wit.log.from", n_log), *key = A.get<uint32_t>("wit.log.key", log_nnz);
-        uint64_t *ptr = A.get<uint64_t>("wit.log.ptr", n_log + 1), *val = A.get<uint64_t>("wit.log.val", 4 * log_nnz);
-        up.send(from, E->log_from.data(), 4 * n_log);
-        up.send(ptr, E->log_ptr.data(), 8 * (n_log + 1));
-        up.send(key, E->log_key.data(), 4 * log_nnz);
-        up.send(val, E->log_val.data(), 32 * log_nnz);
-        WitSrc &s = src[5];  // (evaluated last, after the output)
-        s.n = n_log;
-        s.nparts = 1;
-        s.cls = RS_WITC_LOG;
-        s.from = from;
-        s.ptr[0] = ptr;
-        s.col[0] = key;
-        s.val[0] = val;
-        s.nnz[0] = log_nnz;
-      }
+      if (n_log)  // (src[5]: evaluated last, after the output)
+        wit_stage_log(E, up, E->log_from.data(), E->log_ptr.data(), E->log_key.data(), E->log_val.data(), n_log, log_nnz, src[5]);
       HC(hipStreamSynchronize(E->stc));
     }
     rep->checked[RS_WITC_LOG] = n_log;

@@ -447,5 +447,107 @@ inline int check_witness(const rs_input *in, const rs_output *out, const rs_witn
   return RS_OK;
 }
 
+// ------------------------------------------------------------------ the lift (ABI 14)
+// A wire witness v (one value per wire of `out`) back to one value per --O0 label through the
+// substitution log: entry i says w[log_from[i]] = log_to[i] . w.  The owner of a label is its last entry
+// (constant_eq_simplification logs every row, the map keeps the last); an entry that is not its label's
+// owner is shadowed and defines nothing.  A label with a wire takes the wire's value, a label with an
+// owner the owner's dot product, every other label 0 (free).  The log is in elimination order: an owner
+// entry's owned keys belong to later entries, so one pass from the last entry to the first evaluates
+// every entry after everything it reads; the levels (0: no owned key, else 1 + the deepest owned key's)
+// come out of the same pass.  The device path (lift.hpp) must agree to the bit.
+inline int lift_witness(const rs_output *out, const rs_witness *v, rs_witness **wout, rs_lift_report *rep) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (wout) *wout = nullptr;
+  if (!out || !v || !wout || !rep || (v->n && !v->val) || (out->n_labels && !out->label_to_wire) ||
+      (out->n_log && (!out->log_from || !out->log_to.ptr)) || (out->log_to.nnz && (!out->log_to.col || !out->log_to.val))) {
+    set_error("rs_lift_witness: null argument");
+    return RS_E_INVALID;
+  }
+  memset(rep, 0, sizeof(*rep));
+  const uint64_t L = out->n_labels, Wn = out->n_wires, n = out->n_log;
+  const rs_lc &T = out->log_to;
+  uint64_t p[4];
+  if (!witness_prime(v, p)) { set_error("rs_lift_witness: bad prime or field size"); return RS_E_INVALID; }
+  if (v->n != Wn) {
+    set_error("rs_lift_witness: the witness has " + std::to_string(v->n) + " values, the result " + std::to_string(Wn) + " wires");
+    return RS_E_INVALID;
+  }
+  if (L == 0 || L > 0x7fffffffull) { set_error("rs_lift_witness: the result needs 1 .. 2^31 - 1 labels"); return RS_E_INVALID; }
+  if (v->n == 0 || v->val[0] != 1 || v->val[1] || v->val[2] || v->val[3]) { set_error("rs_lift_witness: w[0] is not 1 (key 0 is the constant)"); return RS_E_INVALID; }
+  for (uint64_t i = 0; i < Wn; ++i)
+    if (!lt4(v->val + 4 * i, p)) { set_error("rs_lift_witness: value " + std::to_string(i) + " is not below the prime"); return RS_E_INVALID; }
+  if (n) {
+    bool ok = T.ptr[0] == 0 && T.ptr[n] == T.nnz;
+    for (uint64_t r = 0; ok && r < n; ++r) ok = T.ptr[r] <= T.ptr[r + 1];
+    if (!ok) { set_error("rs_lift_witness: log_to block: bad row pointers (ptr[0] != 0, decreasing, or ptr[n_log] != nnz)"); return RS_E_INVALID; }
+  }
+  // the owners, one forward pass: owner[s] = 1 + the last entry whose `from` is s
+  std::vector<uint64_t> owner(L, 0);
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t f = out->log_from[i];
+    if (f >= L) { set_error("rs_lift_witness: log entry " + std::to_string(i) + ": `from` is not below the number of labels"); return RS_E_INVALID; }
+    if (f == 0) { set_error("rs_lift_witness: log entry " + std::to_string(i) + ": `from` is the constant (label 0)"); return RS_E_INVALID; }
+    if (out->label_to_wire[f] >= 0) { set_error("rs_lift_witness: log entry " + std::to_string(i) + ": `from` still has a wire"); return RS_E_INVALID; }
+    owner[f] = i + 1;
+  }
+  for (uint64_t e = 0; e < T.nnz; ++e)
+    if (T.col[e] >= L) { set_error("rs_lift_witness: a key is not below the number of labels"); return RS_E_INVALID; }
+  Eval ev;
+  ev.F = host_field(p);
+  ev.n = L;
+  ev.wm.assign(4 * L, 0);
+  for (uint64_t s = 0; s < L; ++s) {
+    const int32_t wire = out->label_to_wire[s];
+    if (wire >= 0) {
+      if ((uint64_t)wire >= Wn) { set_error("rs_lift_witness: a wire is not below n_wires"); return RS_E_INVALID; }
+      hmul(ev.F, v->val + 4 * (uint64_t)wire, ev.F.r2, ev.wm.data() + 4 * s);
+    } else if (owner[s]) {
+      ++rep->lifted;
+    } else {
+      ++rep->free_labels;
+    }
+  }
+  rep->n_labels = L;
+  rep->n_wires = Wn;
+  rep->shadowed = n - rep->lifted;
+  // the entries, last to first
+  std::vector<uint64_t> level(n, 0);
+  uint64_t c[4];
+  for (uint64_t i = n; i-- > 0;) {
+    const uint64_t f = out->log_from[i];
+    if (owner[f] != i + 1) continue;
+    uint64_t lv = 0;
+    for (uint64_t e = T.ptr[i]; e < T.ptr[i + 1]; ++e) {
+      const uint64_t o = owner[T.col[e]];
+      if (!o) continue;
+      if (o - 1 <= i) {
+        set_error("rs_lift_witness: the log is not in elimination order: entry " + std::to_string(i) + " reads the label entry " +
+                  std::to_string(o - 1) + " defines");
+        return RS_E_INVALID;
+      }
+      lv = std::max(lv, level[o - 1] + 1);
+    }
+    level[i] = lv;
+    rep->levels = std::max(rep->levels, lv + 1);
+    rep->entries += T.ptr[i + 1] - T.ptr[i];
+    ev.dot(T, T.ptr[i], T.ptr[i + 1] - T.ptr[i], c);  // (every key is below L: checked above)
+    hmul(ev.F, c, ev.F.r2, ev.wm.data() + 4 * f);
+  }
+  rs_witness *w = (rs_witness *)calloc(1, sizeof(rs_witness));
+  if (!w) { set_error("out of memory"); return RS_E_INTERNAL; }
+  w->prime_id = prime_id_of(p);
+  memcpy(w->prime, p, 32);
+  w->n8 = v->n8;
+  w->n = L;
+  w->val = (uint64_t *)calloc(L, 32);
+  if (!w->val) { witness_free(w); set_error("out of memory"); return RS_E_INTERNAL; }
+  const uint64_t one[4] = {1, 0, 0, 0};
+  for (uint64_t s = 0; s < L; ++s) hmul(ev.F, ev.wm.data() + 4 * s, one, w->val + 4 * s);  // out of Montgomery form
+  *wout = w;
+  rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return RS_OK;
+}
+
 }  // namespace wtns
 }  // namespace rs

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RS_ABI_VERSION 13
+#define RS_ABI_VERSION 14
 
 enum rs_status {
   RS_OK = 0,
@@ -553,6 +553,61 @@ int rs_engine_load_witness(rs_engine *eng, const rs_witness *w);
 int rs_engine_load_wtns(rs_engine *eng, const char *path);
 int rs_engine_check_witness(rs_engine *eng, const rs_input *in, uint32_t what, rs_witness_report *rep);
 int rs_engine_write_wtns(rs_engine *eng, const char *path);
+
+/* ---- ABI 14: the lift.  The way back from a witness of the simplified circuit (one value per wire, what
+ * the witness generator compiled with the --O1 / --O2 circuit writes) to one value per --O0 label, through
+ * the substitution log: entry i says w[log_from[i]] = log_to[i] . w.
+ * Inputs: a result with L = n_labels, Wn = n_wires, label_to_wire, and a log of n entries (original ids,
+ * ascending keys); a wire witness v with v.n == Wn, canonical values and v[0] == 1.
+ * Owner: owner(s) is the largest i with log_from[i] == s, or none (constant_eq_simplification logs every
+ * row; the map keeps the last).  An entry that is not the owner of its `from` is shadowed: it defines
+ * nothing, creates no dependency, and is counted.
+ * Values: w[s] = v[label_to_wire[s]] when label_to_wire[s] >= 0; otherwise log_to[owner(s)] . w when s has
+ * an owner; otherwise 0 (a free label, counted: it was never constrained, or sat in a part that
+ * vanished).  Key 0 is the constant.  A key with coefficient 0 still counts as a key: dependencies follow
+ * key presence.
+ * Level: an owner entry i has level 0 when no key of log_to[i] has an owner, otherwise 1 + the largest
+ * level of its owned keys' owners.  `levels` is 1 + the deepest level, 0 without owner entries.  A level-l
+ * entry reads only wire values, free zeros and values of levels < l.
+ * RS_E_INVALID, with a message naming the cause, nothing produced (*w stays NULL), the engine usable and
+ * its wire witness still resident, for: a null argument; v.n != Wn; a witness prime that is not the
+ * result's (engine calls only: rs_output carries no prime); v[0] != 1 or a value >= the prime;
+ * log_from[i] >= L, == 0, or a label that still has a wire; a key >= L; malformed log row pointers; an
+ * owner entry i with a key whose owner is j <= i (the log is not in elimination order; an entry whose `to`
+ * holds its own `from` is one); on the engine: no result, no resident witness, or a last run without
+ * rs_flags.emit_substitution_log. */
+typedef struct rs_lift_report {
+  uint64_t n_labels, n_wires;
+  uint64_t lifted;      /* labels an owner entry defines          */
+  uint64_t free_labels; /* no wire, no entry: value 0             */
+  uint64_t shadowed;    /* entries whose `from` a later one owns  */
+  uint64_t levels;      /* 1 + the deepest level; 0 without owners */
+  uint64_t entries;     /* (key, value) pairs evaluated: the owner entries' */
+  double in_ms, kernel_ms, total_ms;   /* host twin: in_ms = kernel_ms = 0 */
+} rs_lift_report;
+/* The host twin and the oracle (csrc/wtns_io.hpp, plain 256-bit host arithmetic): owners in one forward
+ * pass, the entries evaluated in one pass from the last index to the first, which the order rule makes
+ * exact.  `out` in either row layout: only n_labels, n_wires, label_to_wire, n_log, log_from and log_to
+ * are read.  *w: library-owned (rs_witness_free), n = L, n8 and the prime as v's. */
+int rs_lift_witness(const rs_output *out, const rs_witness *v, rs_witness **w, rs_lift_report *rep);
+/* The same on the device (csrc/lift.hpp), as a one-shot: an engine for the call, what is read of `out`
+ * and `v` uploaded, the values returned like rs_lift_witness's. */
+int rs_lift_witness_device(int device, const rs_output *out, const rs_witness *v, rs_witness **w, rs_lift_report *rep);
+/* Replaces the engine's resident wire witness (n = n_wires of the last result) with the lifted one (n = L,
+ * same arena: nothing of the result moves); rs_engine_check_witness and rs_engine_write_wtns then work on
+ * it unchanged.  The log goes up once; owners by a 64-bit integer atomicMax, the levels by repeated
+ * entry-parallel passes (one changed-flag read back per pass), one stable radix sort of the owner rows by
+ * level and one scan of their lengths (the virtual row pointers of all levels), then per level the
+ * evaluator of rs_engine_check_witness over the level's rows (RS_WIT_CHUNK) and a lane per row that stores
+ * w[from]: 2 launches a level.  No atomics on field values: values and report equal rs_lift_witness's.  The
+ * resident witness is replaced only after the last error word reads clean.  On a sharded engine every
+ * rank lifts its own complete copy (no collective). */
+int rs_engine_lift_witness(rs_engine *eng, rs_lift_report *rep);
+/* The resident witness, canonical, in library-owned arrays (rs_witness_free); n8 and the prime as loaded. */
+int rs_engine_fetch_witness(rs_engine *eng, rs_witness **w);
+/* The resident witness as it is (no projection): the bytes rs_write_wtns(path, w, NULL) writes; the image
+ * is built on the device and leaves through the buffers and pwrite threads of rs_engine_write_r1cs. */
+int rs_engine_write_wtns_resident(rs_engine *eng, const char *path);
 
 /* Seeded synthetic --O0 systems for benchmarks/tests (see DESIGN.md "Workloads").
  * kind: 0 = mixed (metric circuit, BASELINE configs[4]), 1 = purely linear (configs[1]), 2 = chain

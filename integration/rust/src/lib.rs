@@ -1,10 +1,10 @@
-//! Raw bindings of `include/rs_simplify.h` (ABI 13), one item per C declaration, same order and
+//! Raw bindings of `include/rs_simplify.h` (ABI 14), one item per C declaration, same order and
 //! layout.  The safe wrapper a caller uses is `constraint_list_glue.rs` (the body that replaces
 //! `constraint_list::constraint_simplification::simplification`, constraint_simplification.rs:442).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const RS_ABI_VERSION: c_int = 13;
+pub const RS_ABI_VERSION: c_int = 14;
 pub const RS_COMM_ID_BYTES: usize = 128;
 
 pub const RS_OK: c_int = 0;
@@ -259,6 +259,22 @@ pub struct rs_witness_report {
     pub total_ms: f64,
 }
 
+/// What a lift found (ABI 14): labels an owner entry defines, labels with neither a wire nor an entry
+/// (value 0), entries whose `from` a later one owns, 1 + the deepest level, the (key, value) pairs evaluated.
+#[repr(C)]
+pub struct rs_lift_report {
+    pub n_labels: u64,
+    pub n_wires: u64,
+    pub lifted: u64,
+    pub free_labels: u64,
+    pub shadowed: u64,
+    pub levels: u64,
+    pub entries: u64,
+    pub in_ms: f64,
+    pub kernel_ms: f64,
+    pub total_ms: f64,
+}
+
 /// ABI 12: the last device JSON writer call of either kind on an engine (in + kernel + out = write).
 #[repr(C)]
 pub struct rs_json_stats {
@@ -340,6 +356,14 @@ extern "C" {
     pub fn rs_engine_load_wtns(eng: *mut rs_engine, path: *const c_char) -> c_int;
     pub fn rs_engine_check_witness(eng: *mut rs_engine, inp: *const rs_input, what: u32, rep: *mut rs_witness_report) -> c_int;
     pub fn rs_engine_write_wtns(eng: *mut rs_engine, path: *const c_char) -> c_int;
+    /// The way back (ABI 14): a wire witness lifted to one value per --O0 label through the substitution log;
+    /// the host twin, the one-shot on the device, and on an engine (the resident witness is replaced) ...
+    pub fn rs_lift_witness(out: *const rs_output, v: *const rs_witness, w: *mut *mut rs_witness, rep: *mut rs_lift_report) -> c_int;
+    pub fn rs_lift_witness_device(device: c_int, out: *const rs_output, v: *const rs_witness, w: *mut *mut rs_witness, rep: *mut rs_lift_report) -> c_int;
+    pub fn rs_engine_lift_witness(eng: *mut rs_engine, rep: *mut rs_lift_report) -> c_int;
+    /// ... and the resident witness out again: canonical values (rs_witness_free), or a .wtns as it is.
+    pub fn rs_engine_fetch_witness(eng: *mut rs_engine, w: *mut *mut rs_witness) -> c_int;
+    pub fn rs_engine_write_wtns_resident(eng: *mut rs_engine, path: *const c_char) -> c_int;
     pub fn rs_synth(kind: u32, rows: u64, seed: u64, prime_id: u32, inp: *mut *mut rs_input) -> c_int;
     pub fn rs_flatten_dag(device: c_int, dag: *const rs_dag, inp: *mut *mut rs_input) -> c_int;
     /// The same into the engine's page-locked buffers (the view lives until the next call on `eng`).
