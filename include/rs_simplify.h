@@ -193,7 +193,17 @@ typedef struct rs_stats {
   uint64_t big_main_bytes;     /* algorithmic bytes of the ordered loops (sum over launches)  */
   uint64_t big_finish_bytes;   /* algorithmic bytes of normalisation + composition           */
   uint64_t big_launches;       /* launches of each of the three workgroup kernels            */
-  uint64_t rounds;             /* linear-elimination rounds executed                         */
+  /* Linear-elimination rounds: the reference's calls of linear_simplification
+   * (constraint_simplification.rs:613-646), round 1 included, counted also when a round's list holds
+   * only rows that turned linear in the round before and came out empty -- LESS the reference's
+   * trailing iteration over a list that holds nothing but stale visits: rows an EARLIER round turned
+   * linear and emptied, which a later substitution still finds in the never-pruned map[from]
+   * (is_linear(empty) holds, so :380-394 list them again and the loop runs once more, over nothing).
+   * Finding those visits would mean materialising every map list on the timed path, and such an
+   * iteration substitutes nothing: every result equals the reference's, this count can be one lower
+   * (it is on most inputs whose later rounds turn rows).  tests/round_cases.py rounds_model restates the
+   * definition over pyref. */
+  uint64_t rounds;
   uint64_t n_clusters;
   uint64_t n_substitutions;
   uint64_t max_cluster;

@@ -6,8 +6,18 @@
 // signals are resolved and compared with the unmemoised recursion -- so a memo entry made in an
 // earlier round must never answer for a different (signal, bound) pair later.
 // usage: maplists_check <seed> <rounds> <signals>; prints "ok <checks>" or the first mismatch.
+//
+// File mode, maplists_check --file <path>: the lists of a recorded run of the reference algorithm
+// (tests/round_cases.py maplists_input, from pyref's own map).  The file holds the initial lists
+// (count, then `signal length rows...` each), the number of rounds and per round its queries
+// (`count signals...`: the signals the round substitutes) and its batch (count, then
+// `from length keys...` per substitution, in rank order).  Per round the queries are resolved over the
+// batches of the rounds before it, every non-empty list is printed as `round signal length rows...`,
+// and the batch is added; the test compares the lines with what pyref's map held beyond its initial part.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <fstream>
 #include <random>
 
 #include "maplists.hpp"
@@ -31,7 +41,65 @@ static std::vector<uint32_t> naive(const MapLists &M, const MapLists::Lists &ini
   return out;
 }
 
+static int file_mode(const char *path) {
+  std::ifstream in(path);
+  MapLists::Lists truth;
+  uint64_t n = 0, len = 0;
+  uint32_t s = 0;
+  in >> n;
+  for (uint64_t i = 0; i < n; ++i) {
+    in >> s >> len;
+    std::vector<uint32_t> l(len);
+    for (auto &r : l) in >> r;
+    truth[s] = l;
+  }
+  MapLists M;
+  auto query = [&](const std::vector<uint32_t> &sigs) {
+    for (uint32_t q : sigs) {
+      if (M.minit.count(q)) continue;
+      auto it = truth.find(q);
+      M.minit[q] = it == truth.end() ? std::vector<uint32_t>() : it->second;
+    }
+  };
+  uint64_t rounds = 0;
+  in >> rounds;
+  for (uint64_t r = 0; r < rounds; ++r) {
+    in >> n;
+    std::vector<uint32_t> X(n);
+    for (auto &x : X) in >> x;
+    const MapLists::Lists got = M.resolve(X, query);
+    for (uint32_t x : X) {
+      auto it = got.find(x);
+      if (it == got.end()) continue;
+      printf("%llu %u %zu", (unsigned long long)r, x, it->second.size());
+      for (uint32_t row : it->second) printf(" %u", row);
+      printf("\n");
+    }
+    MapLists::Batch B;
+    B.ptr.push_back(0);
+    in >> n;
+    for (uint64_t j = 0; j < n; ++j) {
+      in >> s >> len;
+      B.from.push_back(s);
+      for (uint64_t t = 0; t < len; ++t) {
+        uint32_t key;
+        in >> key;
+        B.keys.push_back(key);
+      }
+      B.ptr.push_back(B.keys.size());
+    }
+    M.add_batch(std::move(B));
+  }
+  if (!in) {
+    printf("bad input file\n");
+    return 1;
+  }
+  printf("done\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 2 && !strcmp(argv[1], "--file")) return file_mode(argv[2]);
   const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
   const int rounds = argc > 2 ? atoi(argv[2]) : 6;
   const uint32_t S = argc > 3 ? (uint32_t)atoi(argv[3]) : 40;

@@ -279,6 +279,33 @@ def test_map_lists_across_rounds(tmp_path):
             assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
 
 
+def test_map_lists_against_pyref(tmp_path):
+    """csrc/maplists.hpp against the lists the reference algorithm builds, not against its own formula:
+    for every case of round_cases.py, MapLists::resolve over the recorded batches gives, for each signal
+    a later round substitutes, exactly what pyref's never-pruned map[signal] holds beyond its initial
+    list (maplists_check --file).  The cases reach lists appended one to five levels deep, duplicates
+    and rows that are in the initial and in the appended part."""
+    import subprocess
+    import round_cases as rc
+    root = os.path.dirname(HERE)
+    exe = str(tmp_path / "maplists_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(root, "circom_cvm_amd", "csrc"),
+                           os.path.join(HERE, "maplists_check.cpp"), "-o", exe])
+    deepest = 0
+    for case in rc.CASES:
+        rec = rc.record(rc.built(case)[0])
+        path = tmp_path / (case.name + ".txt")
+        path.write_text(rc.maplists_input(rec))
+        out = subprocess.run([exe, "--file", str(path)], capture_output=True, text=True)
+        assert out.returncode == 0, (case.name, out.stdout)
+        want = rc.maplists_expected(rec)
+        assert out.stdout.splitlines() == want + ["done"], case.name
+        deepest = max(deepest, len(want))
+        if case.name.startswith("pos_appended"):
+            assert want, case.name
+    assert deepest >= 5
+
+
 def test_knobs_parse(tmp_path):
     """The environment switches' parser (csrc/knobs.hpp): unset gives the default; "0" and "-3" for a
     knob with min = 1 (RS_SNAP_CHUNK_MB, RS_TAIL_SPLIT: 0 hung the result stream / emptied the first
